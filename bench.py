@@ -14,6 +14,13 @@ one fixed U(-1,1) action sample), `--config dr` = configs[4] (mass/friction rand
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`; every rank owns
 its own 4096 envs (envs are independent: no data-path collective), barrier + synchronize around the
 timed region, max time over ranks, value = total env-steps of all ranks / that time.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (value,
+ms_per_step, the workload). `--full` adds every other measurement to the line: the per-kernel event
+pass and roofline, contact statistics, the committed parity records, the other schemes and configs,
+the learner, the PHCPufferEnv.step rate and the CPU baseline. `--dump-outputs DIR` writes what the
+last timed step handed its caller as DIR/<name>.npy (the inputs are seeded: two builds compare
+output for output).
 """
 import argparse
 import datetime
@@ -89,6 +96,16 @@ def parse(argv=None):
                          "update of the reference-size policy, RCCL gradient all-reduce)")
     ap.add_argument("--no-tracking", action="store_true",
                     help="skip the configs[2] tracking-action leg (throughput + joint-pose L2 vs ref)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure everything else the line can carry: the "
+                         "per-kernel pass with events and the roofline, the contact statistics, the committed parity "
+                         "records, the other schemes and configs, the learner, the PHCPufferEnv.step rate and the CPU "
+                         "baseline (each still has its own --no-* switch). Without it the run sets up, warms up, times "
+                         "--steps steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (obs, reward, raw "
+                         "reward terms, reset / terminate flags and the engine's root / dof / rigid-body state) as "
+                         "DIR/<name>.npy in float32 (rank 0)")
     return ap.parse_args(argv)
 
 
@@ -629,6 +646,57 @@ def cpu_baseline(args, model):
                       f"OpenMP over envs ({threads} threads), {dt:.1f} s"}
 
 
+def headline(args, world, elapsed):
+    """The result line's headline fields: `elapsed` seconds (max over ranks) for args.steps timed steps
+    of args.num_envs envs on each of `world` ranks."""
+    n = args.num_envs
+    return {
+        "metric": "env-steps/sec (4096 SMPL humanoids per GPU)",
+        "value": round(n * args.steps * world / elapsed, 1),
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": DATA[args.config],
+        "config": {"workload": {"standstill": "configs[1]: 4096 SMPL-neutral humanoids, PD stand-still, zero ref motion",
+                                "imitation": "configs[2]: 4096 humanoids over 128 synthetic clips, full PHC reward",
+                                "tracking": "configs[2] with the tracking action stream (SURVEY §8d 3(ii))",
+                                "dr": "configs[4]: 4096 envs, mass/friction randomisation + 3 terrains"}[args.config],
+                   "num_envs_per_gpu": n, "simulate_calls": 2, "substeps_per_simulate": int(sim_substeps(args)),
+                   "sim_dt": 1 / 60, "max_contacts": args.max_contacts,
+                   "scheme": args.scheme, "parallelism": f"replicas{world}"},
+    }
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(ro, out_dir):
+    """What the last step of the timed path handed its caller, as out_dir/<name>.npy (float32): the
+    step's output buffers and the engine state it advanced. Over DUMP_LIMIT_BYTES in all, every array
+    keeps the same fixed, seeded sample of env rows (sorted) and `env_index` names them."""
+    import torch
+    n = ro.args.num_envs
+    eng = ro.eng
+    arrays = {"obs": ro.obs, "reward": ro.rew, "reward_raw": ro.raw, "reset": ro.reset, "terminate": ro.term,
+              "root_states": eng.root_states.view(n, 13), "dof_state": eng.dof_state.view(n, 69, 2),
+              "rb_state": eng.rb_state.view(n, 24, 13)}
+    per_env = sum(4 * (a.numel() // n) for a in arrays.values()) + 4
+    keep = np.arange(n)
+    if per_env * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(12345).choice(n, DUMP_LIMIT_BYTES // per_env, replace=False))
+    idx = torch.as_tensor(keep, device=ro.obs.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.index_select(0, idx).to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "env_index.npy"), keep.astype(np.float32))
+
+
 def main():
     args = parse()
     import torch
@@ -669,6 +737,18 @@ def main():
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ro, args.dump_outputs)
+    if not args.full:
+        # the plain run: the headline alone (the max-over-ranks time, then the line)
+        if world > 1:
+            t = torch.tensor([elapsed], device="cpu" if shared else "cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(args, world, elapsed)), flush=True)
+        return
     nc = ro.eng.num_contacts.cpu().numpy()
     dropped = ro.eng.dropped_contacts.cpu().numpy()
     rows = solver_rows(ro)
@@ -709,8 +789,6 @@ def main():
             except Exception as exc:
                 learner = {"value": None, "error": "rank agreement after the learner leg: " + repr(exc)}
     n = args.num_envs
-    total_steps = n * args.steps * world
-    value = total_steps / elapsed
     if rank == 0:
         if split is not None:  # fused: the one launch is the dominant kernel
             fused_ms = step_ms
@@ -727,26 +805,8 @@ def main():
                     "avg_launch_ms": round(fused_ms, 4), "mfma_util": mfma}
         else:
             roof = phys_roof
-        line = {
-            "metric": "env-steps/sec (4096 SMPL humanoids per GPU)",
-            "value": round(value, 1),
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": DATA[args.config],
-            "config": {"workload": {"standstill": "configs[1]: 4096 SMPL-neutral humanoids, PD stand-still, zero ref motion",
-                                    "imitation": "configs[2]: 4096 humanoids over 128 synthetic clips, full PHC reward",
-                                    "tracking": "configs[2] with the tracking action stream (SURVEY §8d 3(ii))",
-                                    "dr": "configs[4]: 4096 envs, mass/friction randomisation + 3 terrains"}[args.config],
-                       "num_envs_per_gpu": n, "simulate_calls": 2, "substeps_per_simulate": int(sim_substeps(args)),
-                       "sim_dt": 1 / 60, "max_contacts": args.max_contacts,
-                       "scheme": args.scheme, "parallelism": f"replicas{world}"},
+        line = headline(args, world, elapsed)
+        line.update({
             # the physics kernel is bound by the latency of its per-env serial chains (elimination,
             # Gauss-Seidel sweeps, triangular solves) at 2 waves / SIMD, not by HBM or the matrix
             # cores: priced against the FP32 vector / matrix peak with the canonical dense-equivalent
@@ -757,7 +817,7 @@ def main():
                          "capacity": args.max_contacts, "envs_dropping": int((dropped > 0).sum()),
                          "dropped_mean": round(float(dropped.mean()), 4)},
             "unfused_kernels": {"physics_kernel": phys_roof, "imitation_kernel": imit_roof},
-        }
+        })
         if args.config == "standstill" and args.num_envs == 4096:
             line["parity_vs_oracle"] = parity_record("parity_configs1")
         if not args.no_tracking and world == 1 and args.scheme == "default":

@@ -1,5 +1,6 @@
 """Build ``humanoid_amd/libhumanoid_engine.so`` for gfx950 with hipcc (in-tree, travels with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
+import hashlib
 import os
 import re
 import subprocess
@@ -136,7 +137,11 @@ def build(force=False, verbose=False):
             s = os.path.join(CSRC, src)
             o = os.path.join(BUILD, src + (suffix if src in defs else ".o"))
             objs.append(o)
-            cmd = [hipcc] + common + flags + defs.get(src, []) + ["-c", s, "-o", o]
+            # hipcc's default compilation-unit id hashes the source's absolute path into the device
+            # symbols of every anonymous-namespace kernel, so device_code_id() would follow the
+            # checkout directory; an id from the file name keeps it equal in every checkout
+            cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
+            cmd = [hipcc] + common + [cuid] + flags + defs.get(src, []) + ["-c", s, "-o", o]
             _compile(hipcc, cmd, s, o, force and lib == LIB or force and src in defs, hdr_time, verbose)
         _link(hipcc, lib, objs, force)
     return LIB
