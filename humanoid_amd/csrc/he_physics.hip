@@ -110,22 +110,35 @@ HE_DEV int dof_body(int i) { return i < 6 ? 0 : (i - 6) / 3 + 1; }
 // optional per-phase cycle stamps (diagnostic: PhysArgs.stamps != null), lane 0 accumulates
 // s_memtime deltas per phase into stamps[block * HE_STAMP_SLOTS + phase] with a no-return vector
 // atomic add (a load-add-store would put one global round trip into every phase it opens)
+// phase ids of STAMP: the slot of each phase in PhysArgs.stamps. The other end is the PHASES list of
+// tools/phase_profile.py (the same order, the same values); slots 14-19 are carved out of the contact
+// generation, 20-21 out of the rows, 22 out of the PGS, 25-28 are the midpoint bias, 29-31 the TGS
+// iterations
+enum Phase : int {
+    PH_KINEMATICS = 0, PH_INERTIA_RNEA, PH_SUBTREE_SUMS, PH_DRIVES, PH_CRBA, PH_FACTOR, PH_FREE_SOLVE,
+    PH_CONTACT_GEN, PH_ZROWS, PH_DELASSUS, PH_PGS, PH_DU_SOLVE, PH_INTEGRATE, PH_FINAL_FK,
+    PH_LIMIT_SLOTS, PH_SELF_SLOTS, PH_TERRAIN_RANK, PH_TERRAIN_SLOTS, PH_TERRAIN_GEOM, PH_SELF_SEGMENTS,
+    PH_ROWS_JT, PH_ROWS_LT, PH_PGS_SETUP, PH_UNUSED, PH_FUSED,
+    PH_MID_UM, PH_MID_RNEA, PH_MID_SUBTREE, PH_MID_LT, PH_TGS_BIAS, PH_TGS_RHS, PH_TGS_NEXT
+};
+static_assert(PH_FUSED == 24 && PH_TGS_NEXT == 31 && PH_TGS_NEXT < HE_STAMP_SLOTS, "phase ids: tools/phase_profile.py PHASES");
 #ifndef HE_PHASE_STAMPS
 #define HE_PHASE_STAMPS 0  // diagnostic twin library only (build.py PHASES_LIB)
 #endif
+struct Stamps { unsigned long long *slots, t_prev; };  // the env's slots (null: off), the last stamp's cycle count
 #if !HE_PHASE_STAMPS
 #define STAMP(id) \
     do {          \
     } while (0)
 #else
-#define STAMP(id)                                                             \
-    do {                                                                      \
-        if (stamps && lane == 0) {                                            \
-            unsigned long long _t = __builtin_readcyclecounter();             \
-            __hip_atomic_fetch_add(stamps + (id), _t - t_prev, __ATOMIC_RELAXED, \
-                                   __HIP_MEMORY_SCOPE_AGENT);                 \
-            t_prev = _t;                                                      \
-        }                                                                     \
+#define STAMP(id) /* needs `Stamps& st` and `lane` in scope */                        \
+    do {                                                                              \
+        if (st.slots && lane == 0) {                                                  \
+            unsigned long long _t = __builtin_readcyclecounter();                     \
+            __hip_atomic_fetch_add(st.slots + (id), _t - st.t_prev, __ATOMIC_RELAXED, \
+                                   __HIP_MEMORY_SCOPE_AGENT);                         \
+            st.t_prev = _t;                                                           \
+        }                                                                             \
     } while (0)
 #endif
 
@@ -159,6 +172,14 @@ HE_DEV void crf(const float* V, const float* Fm, float* O) {
     O[0] = a.x; O[1] = a.y; O[2] = a.z; O[3] = b.x; O[4] = b.y; O[5] = b.z;
 }
 
+// RNEA body force f = I a + v x* (I v)
+HE_DEV void body_force(const float* I, const float* A, const float* V, float* F) {
+    float IA[6], IV[6], X[6];
+    si_apply(I, A, IA);
+    si_apply(I, V, IV);
+    crf(V, IV, X);
+    for (int x = 0; x < 6; ++x) F[x] = IA[x] + X[x];
+}
 
 // rotation-vector exponential / logarithm for the physics kernel, short instruction sequences (the
 // integration runs them in every TGS position iteration): v_sqrt_f32 and v_rcp_f32 (1 ulp), sin / cos
@@ -357,6 +378,23 @@ HE_DEV int wave_prefix(bool flag, int lane, int& total) {
     return __popcll(below);
 }
 
+// lanes below this one set in a ballot (v_mbcnt)
+HE_DEV int ballot_below(uint64_t bm) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+}
+// wave-wide exclusive prefix of a small count v (0..7): three bit ballots, v_mbcnt per bit
+HE_DEV int wave_prefix3(int v, int& total) {
+    int pre = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint64_t bm = __ballot((v >> k) & 1);
+        pre += ballot_below(bm) << k;
+        total += __popcll(bm) << k;
+    }
+    return pre;
+}
+
 // the value of lane ^ S (S < 32): ds_swizzle in bitmask mode (and 0x1F, xor S)
 template <int S>
 HE_DEV float swizzle_xor(float v) {
@@ -371,15 +409,6 @@ HE_DEV void store_contact(Lds& L, int slot, int b0, int b1, f3 x, f3 n, float ga
 }
 // 16-bit row keys (include/humanoid_engine.h cache layout)
 HE_DEV int row_key(int b0, int b1, int sub, int kind) { return b0 | ((b1 + 2) << 5) | (sub << 10) | (kind << 14); }
-
-// ordered multiply / multiply-add (volatile asm keeps program order against the surrounding LDS
-// reads, so the unrolled sweeps do not hoist every load ahead of the arithmetic)
-template <class T>
-HE_DEV const T* opaque(const T* p) {  // same address through an opaque offset: pins dependent loads
-    int off = 0;
-    asm volatile("" : "+v"(off));
-    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(p) + off);
-}
 
 // Delassus operator on the matrix cores: A = Zh Zh^T as four 32x32 tiles of
 // v_mfma_f32_32x32x2_f32 (exact f32, k-ordered fma chain), K = live dofs two at a time. Lane r
@@ -443,17 +472,20 @@ HE_DEV float reduce_scatter(float (&v)[N]) {
 // readlanes in blocks of four SGPRs (one hazard nop per block), the products on the register pairs
 // (v_pk_fma: half the VALU), the four partial sums of the scalar form (dof i into sum i mod 4),
 // so the result is that form's to the bit
+// over dofs 0..N-1: N = NG, or the leg class's KZ (below), bit for bit the full form when Zh is zero
+// past them (its dropped terms are fma(0, y, s) = s)
+template <int N = NG>
 HE_DEV float zdot_lanes(const regla::ZVec& z, float yl, float y2) {
     using regla::f2v;
     f2v a = f2v{0.f, 0.f}, b = f2v{0.f, 0.f};
-    regla::static_for<0, NG, 4>([&](auto ic) {
+    regla::static_for<0, N, 4>([&](auto ic) {
         constexpr int i0 = decltype(ic)::value;
         float sv[4];
         if constexpr (i0 < 64) regla::rdlane4<i0>(yl, sv);
         else regla::rdlane4<i0 - 64>(y2, sv);
         a = __builtin_elementwise_fma(z.p[i0 >> 1], f2v{sv[0], sv[1]}, a);
-        if constexpr (i0 + 3 < NG) b = __builtin_elementwise_fma(z.p[(i0 >> 1) + 1], f2v{sv[2], sv[3]}, b);
-        else if constexpr (i0 + 2 < NG) b.x = fmaf(ZV(z, i0 + 2), sv[2], b.x);
+        if constexpr (i0 + 3 < N) b = __builtin_elementwise_fma(z.p[(i0 >> 1) + 1], f2v{sv[2], sv[3]}, b);
+        else if constexpr (i0 + 2 < N) b.x = fmaf(ZV(z, i0 + 2), sv[2], b.x);
     });
     return (a.x + a.y) + (b.x + b.y);
 }
@@ -504,33 +536,16 @@ HE_DEV void reduce_scatter_z(const regla::ZVec& z, float x, int lane, float& e1,
 }
 // The rows' support inside the root and the two legs (bodies 0..8: dofs 0..29, the DFS prefix; a body
 // standing or walking on its feet): Zh is zero past dof 29, so the iterations' products run over the
-// first KZ = 32 dofs (dofs 30, 31 exact zeros) with Zh's other 44 registers dead.
-#ifndef HE_TGS_LEGS  // A/B only: 0 runs every env's iterations over all 75 dofs
-#define HE_TGS_LEGS 1
-#endif
-#ifndef HE_TGS_LEGS_ROWS  // A/B only: 0 runs the rows' once-per-step dot products over all 75 dofs
-#define HE_TGS_LEGS_ROWS 1
-#endif
+// first KZ = 32 dofs (dofs 30, 31 exact zeros) with Zh's other 44 registers dead. PhysArgs.full_dofs
+// (HE_TGS_LEGS=0 in the environment) turns the class off at run time.
 constexpr uint32_t kLegBodies = 0x1FFu;
 constexpr int KZ = 32;
 static_assert(smpl::kNB > 9, "the leg prefix is bodies 0..8");
-// zdot_lanes over dofs 0..KZ-1: bit for bit the full form (its dropped terms are fma(0, y, s) = s)
-HE_DEV float zdot_lanes_legs(const regla::ZVec& z, float yl) {
-    using regla::f2v;
-    f2v a = f2v{0.f, 0.f}, b = f2v{0.f, 0.f};
-    regla::static_for<0, KZ, 4>([&](auto ic) {
-        constexpr int i0 = decltype(ic)::value;
-        float sv[4];
-        regla::rdlane4<i0>(yl, sv);
-        a = __builtin_elementwise_fma(z.p[i0 >> 1], f2v{sv[0], sv[1]}, a);
-        b = __builtin_elementwise_fma(z.p[(i0 >> 1) + 1], f2v{sv[2], sv[3]}, b);
-    });
-    return (a.x + a.y) + (b.x + b.y);
-}
 // Zh^T x over dofs 0..KZ-1 into lane = dof: the butterfly's stages inside each 32-lane half (lane bits
 // 4 .. 0: the 32 values to one per lane), then the two halves' partial sums added (lane bit 5). Lanes
 // >= KZ return 0 (e2 = 0: no dof past 63 is on the support). The same sum as reduce_scatter_z's in
-// another association order.
+// another association order: equal to the bit only under solve_tgs' leg-class precondition (at most
+// 32 rows, and rows >= nr with x == 0 and a finite z, so that lanes 32..63 add exact zeros).
 HE_DEV float reduce_scatter_z_legs(const regla::ZVec& z, float x) {
     using regla::f2v;
     const f2v xx = f2v{x, x};
@@ -553,36 +568,6 @@ HE_DEV float reduce_scatter_z_legs(const regla::ZVec& z, float x) {
     swap32(a, b);  // a: lanes < 32 their own half's sum, b: the other half's (lanes >= 32: swapped roles)
     const float e = a + b;
     return regla::lanes<0xFFFFFFFFull>() ? e : 0.f;
-}
-// at most 32 rows (<= 10 contacts): only the rows-0-31 x columns-0-31 tile is needed (one MFMA per
-// dof pair instead of four); rows >= 32 of acol are never read then
-HE_DEV void delassus_mfma32(const regla::ZVec& z, float (&acol)[MAXR], uint32_t live) {
-    f32x16 t00 = {};
-#pragma unroll
-    for (int g = 0; g < NGRP; ++g) {
-        if ((live >> g) & 1u) {
-#pragma unroll
-            for (int h = 0; h < 4; h += 2) {
-                const int k0 = 4 * g + h;
-                if (k0 < NG) {
-                    float p0 = ZV(z, k0), p1 = k0 + 1 < NG ? ZV(z, k0 + 1 < NG ? k0 + 1 : 0) : 0.f;
-                    swap32(p0, p1);
-                    t00 = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p0, t00, 0, 0, 0);
-                }
-            }
-        }
-    }
-    const f32x16 zero = {};
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int r = (v & 3) + 8 * (v >> 2);
-        float a = t00[v], b = zero[v];
-        swap32(a, b);  // a: A[r][lane], b: A[r + 4][lane] (lanes >= 32: zero)
-        acol[r] = a;
-        acol[r + 4] = b;
-        if (32 + r < MAXR) acol[32 + r < MAXR ? 32 + r : 0] = 0.f;
-        if (36 + r < MAXR) acol[36 + r < MAXR ? 36 + r : 0] = 0.f;
-    }
 }
 // 33-48 rows (11-16 contacts): 16x16x4 tiles over three row blocks instead of four 32x32 tiles
 // (9 x 32 cycles per four dofs instead of 8 x 64). Operands: a 4x4 transpose of (register,
@@ -627,6 +612,9 @@ HE_DEV void delassus_mfma48(const regla::ZVec& z, float (&acol)[MAXR], uint32_t 
 #pragma unroll
     for (int r = 48; r < MAXR; ++r) acol[r] = 0.f;
 }
+// The four 32x32 tiles; WIDE = false (at most 32 rows, <= 10 contacts): only the rows-0-31 x
+// columns-0-31 tile (one MFMA per dof pair instead of four), rows >= 32 of acol zero
+template <bool WIDE>
 HE_DEV void delassus_mfma(const regla::ZVec& z, float (&acol)[MAXR], uint32_t live) {
     f32x16 t00 = {}, t01 = {}, t10 = {}, t11 = {};
 #pragma unroll
@@ -639,9 +627,11 @@ HE_DEV void delassus_mfma(const regla::ZVec& z, float (&acol)[MAXR], uint32_t li
                     float p0 = ZV(z, k0), p1 = k0 + 1 < NG ? ZV(z, k0 + 1 < NG ? k0 + 1 : 0) : 0.f;
                     swap32(p0, p1);
                     t00 = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p0, t00, 0, 0, 0);
-                    t01 = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p1, t01, 0, 0, 0);
-                    t10 = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p0, t10, 0, 0, 0);
-                    t11 = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p1, t11, 0, 0, 0);
+                    if constexpr (WIDE) {
+                        t01 = __builtin_amdgcn_mfma_f32_32x32x2f32(p0, p1, t01, 0, 0, 0);
+                        t10 = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p0, t10, 0, 0, 0);
+                        t11 = __builtin_amdgcn_mfma_f32_32x32x2f32(p1, p1, t11, 0, 0, 0);
+                    }
                 }
             }
         }
@@ -650,8 +640,8 @@ HE_DEV void delassus_mfma(const regla::ZVec& z, float (&acol)[MAXR], uint32_t li
     for (int v = 0; v < 16; ++v) {
         const int r = (v & 3) + 8 * (v >> 2);
         float a = t00[v], b = t01[v], c = t10[v], d = t11[v];
-        swap32(a, b);  // a: A[r][lane], b: A[r + 4][lane]
-        swap32(c, d);  // c: A[32 + r][lane], d: A[36 + r][lane]
+        swap32(a, b);  // a: A[r][lane], b: A[r + 4][lane] (narrow: lanes >= 32 zero)
+        if constexpr (WIDE) swap32(c, d);  // c: A[32 + r][lane], d: A[36 + r][lane]
         acol[r] = a;
         acol[r + 4] = b;
         if (32 + r < MAXR) acol[32 + r < MAXR ? 32 + r : 0] = c;
@@ -701,8 +691,6 @@ HE_DEV void pgs_sweep_tgs(regla::f2v& ch, float& dvec, float& lo, const float (&
     }
 }
 
-// CRBA straight into registers: lane j owns column j, H[i][j] = S_j . IS_i for j in chain(i)
-// (compile-time lane masks), plus armature and the implicit-drive terms on the diagonal
 // ---- contact-row helpers (rows phase)
 // bodies touched by dof group g (4 dofs), as a mask over bodies
 struct GroupBodies {
@@ -718,16 +706,6 @@ struct GroupBodies {
 constexpr GroupBodies kGroupBodiesT{};
 constexpr const uint32_t* kGroupBodies = kGroupBodiesT.m;
 
-// joint b's data for the row Jacobian: body origin (3), its 3 joint axes (9), their free velocities (3)
-HE_DEV void zrow_load(const Lds& L, int b, float (&d)[15]) {
-    const Lds& Lg = *opaque(&L);
-    for (int x = 0; x < 3; ++x) d[x] = Lg.pw[b][x];
-    for (int c = 0; c < 3; ++c) {
-        const int i = 6 + 3 * (b - 1) + c;
-        for (int x = 0; x < 3; ++x) d[3 + 3 * c + x] = Lg.S[i][x];
-        d[12 + c] = Lg.uf[i];
-    }
-}
 // z = J_r^T on the matrix cores: C[i][r] = S_i . u_r with u_r = (rho, dd) of row r (lane r), as
 // v_mfma_f32_32x32x2_f32 tiles over the dof blocks of 32 that hold a live body (A = S from LDS, B =
 // the rows' 6-vectors redistributed by one permlane32 swap per k step). The two row tiles of a
@@ -791,34 +769,6 @@ HE_DEV void zrows_mfma(regla::ZVec& z, uint32_t lb, uint32_t anc0, uint32_t anc1
     for (int i = 0; i < NG; ++i) ZV(z, i) *= sg[i < 6 ? 0 : (i - 6) / 3 + 1];
 }
 
-// z_i = S_i . (rho, dd) = a_i . ((x - p_b) x dd) for joint b's three dofs, bodies in order with
-// the next live body's data read while this one is computed
-template <int B>
-HE_DEV void zrow_bodies(regla::ZVec& z, float (&bacc)[4], uint32_t lb, uint32_t anc0, uint32_t anc1, f3 cx, f3 dd,
-                        const Lds& L, const float (&cur)[15]) {
-    if constexpr (B < NB) {
-        float nxt[15];
-        if constexpr (B + 1 < NB) {
-            if ((lb >> (B + 1)) & 1u) zrow_load(L, B + 1, nxt);
-            else
-                for (int x = 0; x < 15; ++x) regla::undef_reg(nxt[x]);  // never read: no zeros
-        }
-        constexpr int i0 = 6 + 3 * (B - 1);
-        if ((lb >> B) & 1u) {
-            const float sgn = (float)((anc0 >> B) & 1u) - (float)((anc1 >> B) & 1u);
-            const f3 v = cross3(cx - f3{cur[0], cur[1], cur[2]}, dd) * sgn;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                ZV(z, i0 + c) = cur[3 + 3 * c] * v.x + cur[4 + 3 * c] * v.y + cur[5 + 3 * c] * v.z;
-                bacc[c] = fmaf(ZV(z, i0 + c), cur[12 + c], bacc[c]);
-            }
-        } else {
-            ZV(z, i0) = 0.f; ZV(z, i0 + 1) = 0.f; ZV(z, i0 + 2) = 0.f;
-        }
-        asm volatile("" : "+v"(z.p[i0 >> 1]), "+v"(z.p[(i0 + 2) >> 1]), "+v"(bacc[0]), "+v"(bacc[1]), "+v"(bacc[2]));
-        zrow_bodies<B + 1>(z, bacc, lb, anc0, anc1, cx, dd, L, nxt);
-    }
-}
 template <int I, int N = NG>
 HE_DEV void scale_rows(regla::ZVec& z, float sdl, float sdl2) {
     if constexpr (I < N) {
@@ -856,28 +806,11 @@ HE_DEV float znorm2(const regla::ZVec& z) {
     return (dacc[0] + dacc[1]) + (dacc[2] + dacc[3]);
 }
 
-// CRBA: one row I from its IS_I (registers)
-template <int I>
-HE_DEV void crba_row(regla::RegMat& M, const float (&Sj)[6], const float (&Sj2)[6], float dadd, float dadd2,
-                     const float* IS) {
-    using namespace regla;
-    float h = lanes<smpl::kAncLo[I]>() ? dot6(Sj, IS) : 0.f;
-    if constexpr (I < 64) h = lanes<1ull << I>() ? h + dadd : h;  // armature + implicit drive
-    asm volatile("" : "+v"(h));
-    mc_set<I>(M, h);
-    if constexpr (I >= 64) {
-        float h2 = lanes<(uint64_t)smpl::kAncHi[I]>() ? dot6(Sj2, IS) : 0.f;
-        h2 = lanes<1ull << (I - 64)>() ? h2 + dadd2 : h2;
-        asm volatile("" : "+v"(h2));
-        mc2_set<I - 64>(M, h2);
-    }
-}
-
 // CRBA on the matrix cores: H = IS^T S as v_mfma_f32_32x32x2_f32 tiles (rows i, columns j, K = the
 // six spatial components in three steps), lower block triangle only: 6 tiles, 18 MFMAs. Operands
 // come straight from LDS (lane l: IS_{32R + l%32}[2s + l/32] and S_{32C + l%32}[2s + l/32]). One
 // v_permlane32_swap per register pair of a row block's column-tile pair lands "lane j holds column
-// j" (RegMat), then the ancestor masks and the diagonal addends as in crba_row.
+// j" (RegMat), then the diagonal addends (armature + implicit drive).
 template <int RB>
 HE_DEV void crba_tile_rows(regla::RegMat& M, const f32x16& ta, const f32x16& tb) {
 #pragma unroll
@@ -1034,6 +967,20 @@ template <int K>
 HE_DEV int jump_of(uint32_t jp) {  // byte K of the lane's packed entry, sign-extended (v_bfe_i32)
     return (int)(int8_t)(jp >> (8 * K));
 }
+// y_b <- the sum of y over body b's chain below the root (lane = body; jp: the lane's packed jump
+// entry, 0xFFFFFFFF for none), by pointer jumping; the root's own term is added by the caller
+HE_DEV void chain_prefix6(uint32_t jp, int lane, float (&y)[6]) {
+    regla::static_for<0, kKinRounds, 1>([&](auto kc) {
+        const int j = jump_of<decltype(kc)::value>(jp);
+        const int src = j < 0 ? lane : j;
+        float ya[6];
+#pragma unroll
+        for (int x = 0; x < 6; ++x) ya[x] = __shfl(y[x], src, W);
+        if (j >= 0)
+#pragma unroll
+            for (int x = 0; x < 6; ++x) y[x] += ya[x];
+    });
+}
 
 // World poses and spatial velocities, lane = body, by pointer jumping: X_b <- X_{J_k(b)} o X_b and
 // V_b <- V_b + V_{J_k(b)} with J_k the 2^k-th ancestor, four rounds for chains of up to 16 bodies
@@ -1079,10 +1026,7 @@ HE_DEV void kinematics(Lds& L, const he_model& m, int lane, const he_sim_params&
             q = qmul(qa, q);
         }
     };
-    jump(std::integral_constant<int, 0>{});
-    jump(std::integral_constant<int, 1>{});
-    jump(std::integral_constant<int, 2>{});
-    if constexpr (kKinRounds == 4) jump(std::integral_constant<int, 3>{});
+    regla::static_for<0, kKinRounds, 1>(jump);
     if (b != 0) {  // root-frame pose of the chain -> world axes, origin about o
         p = qapply(qr, p);
         q = qmul(qr, q);
@@ -1099,21 +1043,7 @@ HE_DEV void kinematics(Lds& L, const he_model& m, int lane, const he_sim_params&
     float vj[6];  // the joint's own velocity S_b u_b (RNEA velocity-product term below)
 #pragma unroll
     for (int x = 0; x < 6; ++x) vj[x] = V[x];
-    auto vjump = [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        const int j = jump_of<K>(jp);
-        const int src = j < 0 ? lane : j;
-        float Va[6];
-#pragma unroll
-        for (int x = 0; x < 6; ++x) Va[x] = __shfl(V[x], src, W);
-        if (j >= 0)
-#pragma unroll
-            for (int x = 0; x < 6; ++x) V[x] += Va[x];
-    };
-    vjump(std::integral_constant<int, 0>{});
-    vjump(std::integral_constant<int, 1>{});
-    vjump(std::integral_constant<int, 2>{});
-    if constexpr (kKinRounds == 4) vjump(std::integral_constant<int, 3>{});
+    chain_prefix6(jp, lane, V);
     if (b != 0) {  // plus the root's own velocity
 #pragma unroll
         for (int x = 0; x < 6; ++x) V[x] += L.u0[x];
@@ -1136,21 +1066,7 @@ HE_DEV void kinematics(Lds& L, const he_model& m, int lane, const he_sim_params&
         } else {
             crm(V, vj, A);
         }
-        auto ajump = [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            const int j = jump_of<K>(jp);
-            const int src = j < 0 ? lane : j;
-            float Aa[6];
-#pragma unroll
-            for (int x = 0; x < 6; ++x) Aa[x] = __shfl(A[x], src, W);
-            if (j >= 0)
-#pragma unroll
-                for (int x = 0; x < 6; ++x) A[x] += Aa[x];
-        };
-        ajump(std::integral_constant<int, 0>{});
-        ajump(std::integral_constant<int, 1>{});
-        ajump(std::integral_constant<int, 2>{});
-        if constexpr (kKinRounds == 4) ajump(std::integral_constant<int, 3>{});
+        chain_prefix6(jp, lane, A);
         if (b != 0) {  // plus the base acceleration
 #pragma unroll
             for (int x = 0; x < 6; ++x) A[x] += A0[x];
@@ -1178,13 +1094,6 @@ HE_DEV void kinematics(Lds& L, const he_model& m, int lane, const he_sim_params&
     static_assert(NG - W <= W && NG - W > 0, "a second set of lanes covers dofs 64..NG-1");
     if (lane < NG - W) axis(W + lane, false);
     sync();
-}
-
-// y <- L^-1 y for the lane's rows (see regla::solve_L_rows / solve_L_gather)
-HE_DEV void solve_L(const float (&r1)[regla::kRowRegs], const float (&r2)[regla::kRowRegs], int lane, float& yl,
-                    float& y2) {
-    (void)lane;
-    regla::solve_L_rows<0>(r1, r2, yl, y2);
 }
 
 // lane i's packed row of L (dof i) and the row of dof 64 + i (lanes >= NH read row 64 and never
@@ -1221,9 +1130,17 @@ HE_DEV void mid_lt(Lds& L, const BodyTopo& T, int lane, float c1, float c2) {
     sync();
 }
 
-HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_params& p, unsigned long long* stamps,
-                               unsigned long long& t_prev) {
-    (void)stamps; (void)t_prev;
+// joint b's own velocity S_b u_b at the generalized velocity vel (the root's S are the unit axes)
+HE_DEV void joint_velocity(const Lds& L, const BodyTopo& T, int b, const float* vel, float (&vj)[6]) {
+    if (b == 0) {
+        for (int x = 0; x < 6; ++x) vj[x] = vel[x];
+    } else {
+        const int d0 = T.dof0[b];
+        const float u0_ = vel[d0], u1_ = vel[d0 + 1], u2_ = vel[d0 + 2];
+        for (int x = 0; x < 6; ++x) vj[x] = L.S[d0][x] * u0_ + L.S[d0 + 1][x] * u1_ + L.S[d0 + 2][x] * u2_;
+    }
+}
+HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_params& p, Stamps& st) {
     using namespace regla;
     const float dt = p.dt;
     {  // um = u0 + (L^-1 D^-1/2 yh) / 2, the midpoint of u0 and the explicit free velocity
@@ -1232,13 +1149,13 @@ HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_para
         float t1 = L.yh[lane] * L.sDinv[lane];
         float t2 = lane < NH ? L.yh[64 + lane] * L.sDinv[64 + lane] : 0.f;
         __builtin_amdgcn_s_setprio(kPrioSerial);  // a serial chain (level sweep)
-        solve_L(r1, r2, lane, t1, t2);
+        regla::solve_L_rows<0>(r1, r2, t1, t2);  // y <- L^-1 y for the lane's rows
         __builtin_amdgcn_s_setprio(kPrioDefault);
         L.uf[lane] = L.u0[lane] + 0.5f * t1;
         if (lane < NH) L.uf[64 + lane] = L.u0[64 + lane] + 0.5f * t2;
     }
     sync();
-    STAMP(25);
+    STAMP(PH_MID_UM);
     const bool bl = lane < NB;
     const int b = bl ? lane : 0;
     // velocities and bias accelerations at um by pointer jumping over the chain, as the kinematics
@@ -1247,34 +1164,11 @@ HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_para
     float Fb[6];
     {
         const uint32_t jp = bl ? T.jump4[b] : 0xFFFFFFFFu;
-        float vj[6];  // the joint's own velocity S_b um_b (the root's S are the unit axes)
-        if (b == 0) {
-            for (int x = 0; x < 6; ++x) vj[x] = L.uf[x];
-        } else {
-            const int d0 = T.dof0[b];
-            const float u0_ = L.uf[d0], u1_ = L.uf[d0 + 1], u2_ = L.uf[d0 + 2];
-            for (int x = 0; x < 6; ++x) vj[x] = L.S[d0][x] * u0_ + L.S[d0 + 1][x] * u1_ + L.S[d0 + 2][x] * u2_;
-        }
+        float vj[6];
+        joint_velocity(L, T, b, L.uf, vj);
         float V[6];
         for (int x = 0; x < 6; ++x) V[x] = vj[x];
-        auto prefix6 = [&](float (&y)[6]) {
-            auto round = [&](auto kc) {
-                constexpr int K = decltype(kc)::value;
-                const int j = jump_of<K>(jp);
-                const int src = j < 0 ? lane : j;
-                float ya[6];
-#pragma unroll
-                for (int x = 0; x < 6; ++x) ya[x] = __shfl(y[x], src, W);
-                if (j >= 0)
-#pragma unroll
-                    for (int x = 0; x < 6; ++x) y[x] += ya[x];
-            };
-            round(std::integral_constant<int, 0>{});
-            round(std::integral_constant<int, 1>{});
-            round(std::integral_constant<int, 2>{});
-            if constexpr (kKinRounds == 4) round(std::integral_constant<int, 3>{});
-        };
-        prefix6(V);
+        chain_prefix6(jp, lane, V);
         const float um6[6] = {L.uf[0], L.uf[1], L.uf[2], L.uf[3], L.uf[4], L.uf[5]};
         if (b != 0)
             for (int x = 0; x < 6; ++x) V[x] += um6[x];
@@ -1286,20 +1180,16 @@ HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_para
         } else {
             crm(V, vj, A);  // joint b's velocity-product term V_b x S_b um_b
         }
-        prefix6(A);
+        chain_prefix6(jp, lane, A);
         if (b != 0)
             for (int x = 0; x < 6; ++x) A[x] += A0[x];
-        float IA[6], IV[6], X[6];
-        si_apply(L.Ib[b], A, IA);
-        si_apply(L.Ib[b], V, IV);
-        crf(V, IV, X);
-        for (int x = 0; x < 6; ++x) Fb[x] = IA[x] + X[x];
+        body_force(L.Ib[b], A, V, Fb);
     }
     sync();
     if (bl)
         for (int x = 0; x < 6; ++x) L.Acc[b][x] = Fb[x];
     sync();
-    STAMP(26);
+    STAMP(PH_MID_RNEA);
     // subtree sums of the new body forces, in place by body levels (as the first bias's): +4.8 %
     // against the per-dof-lane sums below (r03 A/B, profiles/r03/ab_pred_levels.txt, under the
     // two-wave bound that lets it fit)
@@ -1310,9 +1200,9 @@ HE_DEV void bias_midpoint(Lds& L, const BodyTopo& T, int lane, const he_sim_para
     };
     float c1 = corr(lane);
     float c2 = lane < NH ? corr(64 + lane) : 0.f;
-    STAMP(27);
+    STAMP(PH_MID_SUBTREE);
     mid_lt(L, T, lane, c1, c2);
-    STAMP(28);
+    STAMP(PH_MID_LT);
 }
 
 // lane predicates of the TGS iterations' helpers as constant exec masks, rematerialised at each use
@@ -1336,37 +1226,14 @@ HE_DEV void tgs_bias_at(Lds& L, const BodyTopo& T, int lane, const he_sim_params
     const bool bl = lanes_body();
     const int b = bl ? lane : 0;
     const uint32_t jp = bl ? T.jump4[b] : 0xFFFFFFFFu;
-    auto prefix6 = [&](float (&y)[6]) {
-        auto round = [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            const int j = jump_of<K>(jp);
-            const int src = j < 0 ? lane : j;
-            float ya[6];
-#pragma unroll
-            for (int x = 0; x < 6; ++x) ya[x] = __shfl(y[x], src, W);
-            if (j >= 0)
-#pragma unroll
-                for (int x = 0; x < 6; ++x) y[x] += ya[x];
-        };
-        round(std::integral_constant<int, 0>{});
-        round(std::integral_constant<int, 1>{});
-        round(std::integral_constant<int, 2>{});
-        if constexpr (kKinRounds == 4) round(std::integral_constant<int, 3>{});
-    };
     {  // joint velocities vj = S_b u_b and body velocities V = prefix of vj (+ the root's)
         float vj[6];
-        if (b == 0) {
-            for (int x = 0; x < 6; ++x) vj[x] = vel[x];
-        } else {
-            const int d0 = T.dof0[b];
-            const float u0_ = vel[d0], u1_ = vel[d0 + 1], u2_ = vel[d0 + 2];
-            for (int x = 0; x < 6; ++x) vj[x] = L.S[d0][x] * u0_ + L.S[d0 + 1][x] * u1_ + L.S[d0 + 2][x] * u2_;
-        }
+        joint_velocity(L, T, b, vel, vj);
         if (bl)
             for (int x = 0; x < 6; ++x) L.F[b][x] = vj[x];
         float V[6];
         for (int x = 0; x < 6; ++x) V[x] = vj[x];
-        prefix6(V);
+        chain_prefix6(jp, lane, V);
         if (b != 0)
             for (int x = 0; x < 6; ++x) V[x] += vel[x];
         if (bl)
@@ -1385,7 +1252,7 @@ HE_DEV void tgs_bias_at(Lds& L, const BodyTopo& T, int lane, const he_sim_params
                 crm(L.V[b], L.F[b], A);  // joint b's velocity-product term V_b x S_b u_b
             }
         }
-        prefix6(A);
+        chain_prefix6(jp, lane, A);
         if (b != 0) {
             const f3 vxw = cross3(f3{vel[3], vel[4], vel[5]}, f3{vel[0], vel[1], vel[2]});
             A[3] += vxw.x - p.gravity[0]; A[4] += vxw.y - p.gravity[1]; A[5] += vxw.z - p.gravity[2];
@@ -1574,44 +1441,32 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
     sync();
 }
 
-// ---------------------------------------------------------------------------------- one substep
-template <bool TGS>
-HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
-                    const float* mass_scale, float mu, int tkind, unsigned long long* stamps,
-                    unsigned long long& t_prev, bool first, bool last) {
-    using namespace regla;
-    // the launch arguments through an opaque offset too: their fields are re-read (scalar loads
-    // from the kernarg segment) where used instead of being held in SGPRs across the substep loop
-    int ao = 0;
-    asm volatile("" : "+s"(ao));
-    const PhysArgs& a = *reinterpret_cast<const PhysArgs*>(reinterpret_cast<const char*>(&a0) + ao);
-    // opaque per substep: keeps the compiler from hoisting ~1k uniform model loads out of the
-    // substep loop into SGPRs (which then spill into VGPR lanes)
-    // (an opaque byte offset rather than an opaque pointer: the pointer keeps its global address
-    // space, so the loads stay global_load / s_load instead of flat_load)
-    int mo = 0;
-    asm volatile("" : "+s"(mo));
-    const he_model& m = *reinterpret_cast<const he_model*>(reinterpret_cast<const char*>(mp) + mo);
-    // likewise an opaque VGPR base for LDS: addresses become base + immediate offset instead of
-    // hundreds of hoisted uniform address constants
-    int lds_off = 0;
-    asm volatile("" : "+v"(lds_off));
-    Lds& L = *reinterpret_cast<Lds*>(reinterpret_cast<char*>(&L0) + lds_off);
-    // and the lane id: the many per-lane predicates of the unrolled algebra are then rebuilt
-    // next to their use instead of being hoisted as loop invariants
-    asm volatile("" : "+v"(lane));
-    const BodyTopo& T = L.T;
-    const he_sim_params& p = a.p;
-    const float dt = p.dt;
-    // TGS (solver_type 1, oracle substep_tgs): K position iterations of hs = dt / K on this step's
-    // factor and contact set; PGS: one step of hs = dt
-    const int K = TGS ? (p.solver_iterations < 1 ? 1 : (p.solver_iterations > kTgsMaxIt ? kTgsMaxIt : p.solver_iterations)) : 1;
-    const float hs = TGS ? dt / (float)K : dt;
-    __builtin_amdgcn_s_setprio(kPrioDefault);
-    kinematics<true>(L, m, lane, a.p, !first);
-    __builtin_amdgcn_s_setprio(kPrioDefault);
-    STAMP(0);
-    // ---- body spatial inertias about o + RNEA body forces (gravity as base acceleration)
+// ---------------------------------------------------------------------------------- substep phases
+// The phases of one substep, in the order substep() runs them, each forced inline. Values that cross
+// a phase boundary in registers travel in the small structs below (SROA dissolves them), all else in
+// LDS. Every phase ends on a sync() unless its comment says otherwise. LDS words that serve twice
+// within a substep (the contract a kernel split has to keep):
+//   IS   CRBA operand until factor_free; then gen_contacts' candidate gaps / bodies / rank order
+//        (cand_gaps, cand_bodies, cand_order); from row_setup to contact_forces_out the rows' linear
+//        directions (row_dirs, over the rank order's words: the reduction is done by then)
+//   lam  the previous solve's impulses until substep() has read them (lam_prev); self_pairs' survivor
+//        list; from row_setup to the solve's set-up the rows' friction bound weights; then the new
+//        impulses
+//   Ic / Ib  composite / own inertias; from terrain_candidates to the end of gen_contacts the bodies'
+//        world segments live in Ib (PGS) or Ic (TGS: Ib keeps the own inertias for tgs_bias_at)
+//   Acc  RNEA accelerations until body_forces; the midpoint's body forces; from terrain_candidates the
+//        bounding spheres (bsph) and, after them, build_rows' patch radii (patch_radius), both dead
+//        after row_setup; then tgs_bias_at's body forces
+//   F    subtree forces until bias_midpoint's correction; build_rows' patch normals and centroids
+//        until row_setup; then tgs_bias_at's joint velocities
+//   V    body velocities until bias_midpoint / the row set-up; tgs_bias_at's scratch after
+//   uf   PGS: midpoint velocity, then the solved velocity; TGS: the bias at the working velocity
+
+// body spatial inertias about o + RNEA body forces, gravity as base acceleration (oracle
+// body_inertia and the force pass of rnea), lane = body. Reads qw, pw, V, Acc of the kinematics;
+// writes Ic (own inertia: the subtree sums accumulate in place), Ib (the same, for the midpoint's and
+// the TGS iterations' second RNEA) and F (body force).
+HE_DEV void body_forces(Lds& L, const he_model& m, const he_sim_params& p, int lane, const float* mass_scale) {
     if (lane < NB) {
         int b = lane;
         float ms = mass_scale ? mass_scale[b] : 1.f;
@@ -1639,20 +1494,18 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
         o10[4] = I[0][0]; o10[5] = I[1][1]; o10[6] = I[2][2]; o10[7] = I[0][1]; o10[8] = I[0][2]; o10[9] = I[1][2];
         if (p.bias_midpoint)  // the body's own inertia for the midpoint's second RNEA (Ib is free until
             for (int x = 0; x < 10; ++x) L.Ib[b][x] = o10[x];  // the contact phase's segments)
-        float IA[6], IV[6], X[6];
-        si_apply(o10, L.Acc[b], IA);
-        si_apply(o10, L.V[b], IV);
-        crf(L.V[b], IV, X);
-        for (int x = 0; x < 6; ++x) L.F[b][x] = IA[x] + X[x];  // body force f_b (accumulated in place)
+        body_force(o10, L.Acc[b], L.V[b], L.F[b]);  // body force f_b (accumulated in place)
     }
     sync();
-    STAMP(1);
-    // ---- subtree sums: F_b (forces) and composite inertias, in place by body levels
-    __builtin_amdgcn_s_setprio(kPrioDefault);
-    subtree_levels<16, smpl::kNumBodyLevels - 2>(&L.F[0][0], &L.Ic[0][0], lane);
-    __builtin_amdgcn_s_setprio(kPrioDefault);
-    STAMP(2);
-    // ---- bias forces, IS_i = Ic S_i, drives
+}
+
+// Bias forces, IS_i = Ic S_i and the implicit PD drives (oracle: the drive block), lane = dof, then
+// dofs 64..74 on lanes 0..10. Writes IS, dforce (PGS: the drive torque; TGS: the scaled stiffness),
+// uf (TGS: the bias at u0), rhs, coef. The per-dof body stays a lambda that captures by reference:
+// as a function taking hs and limmask by value, the PGS kernel came out with one v_fma and one v_mul
+// fewer and one v_sub more (a product contracted another way), and its results left the parent's bits.
+template <bool TGS>
+HE_DEV void drive_terms(Lds& L, const he_model& m, const he_sim_params& p, int lane, float hs) {
     const uint32_t limmask = p.joint_limits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)L.limmask) : 0u;
     // lane = dof (then dofs 64..74 on lanes 0..10), the root's six dofs selected out: no loop,
     // no root branch, saturation by selects
@@ -1687,381 +1540,418 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     dof_terms(lane, true);
     if (lane < NG - W) dof_terms(W + lane, false);
     sync();
-    STAMP(3);
-    // ---- CRBA straight into registers: lane j owns column j, H[i][j] = S_j . IS_i
+}
+
+// CRBA straight into registers (lane j owns column j, H[i][j] = S_j . IS_i), the sparse LTDL in
+// registers (RBDA 6.5, deepest dof first) with the free-velocity right-hand side y = L^-T (dt rhs)
+// carried through the elimination. Leaves Lp (the packed factor), sDinv and yh in LDS; the mass
+// matrix never leaves the registers of this function. IS is dead after it.
+HE_DEV void factor_free(Lds& L, const he_model& m, int lane, float hs, Stamps& st) {
+    using namespace regla;
     RegMat M;
     {
-        float Sj[6], Sj2[6];
-        for (int x = 0; x < 6; ++x) { Sj[x] = L.S[lane][x]; Sj2[x] = lane < NH ? L.S[64 + lane][x] : 0.f; }
         // per-lane diagonal addend (dof = lane, and 64 + lane on lanes < 11), loaded once
         const float dadd = lane >= 6 ? m.armature[lane >= 6 ? lane - 6 : 0] + hs * L.coef[lane] : 0.f;
         const float dadd2 = lane < NH ? m.armature[lane < NH ? 58 + lane : 0] + hs * L.coef[64 + lane] : 0.f;
-        (void)Sj; (void)Sj2;
         crba_mfma(M, L, lane, dadd, dadd2);
     }
-    STAMP(4);
-    // ---- sparse LTDL in registers (RBDA 6.5, deepest dof first); L leaves through LDS, packed
-    // with the free-velocity right-hand side y = L^-T (dt*rhs) carried through the elimination
+    STAMP(PH_CRBA);
     float yl = L.rhs[lane], y2 = lane < NH ? L.rhs[64 + lane] : 0.f;
-    {
-        float Dl = 1.f, D2 = 1.f;
-        __builtin_amdgcn_s_setprio(kPrioSerial);
-        factor_pipelined(M, Dl, D2, L.Lp, L.T.dof_depth[lane], lane < NH ? L.T.dof_depth[64 + lane] : 0, yl, y2);
-        __builtin_amdgcn_s_setprio(kPrioDefault);
-        L.sDinv[lane] = 1.0f / sqrtf(Dl);
-        if (lane < NH) L.sDinv[64 + lane] = 1.0f / sqrtf(D2);
-        // the free velocity is not formed here: the contact bias takes z.u0 + zh.yh, and one L^-1
-        // sweep after the solver gives uf = u0 + L^-1 D^-1/2 (yh + Zh^T lambda)
-        L.yh[lane] = yl * (1.0f / sqrtf(Dl));
-        if (lane < NH) L.yh[64 + lane] = y2 * (1.0f / sqrtf(D2));
+    float Dl = 1.f, D2 = 1.f;
+    __builtin_amdgcn_s_setprio(kPrioSerial);
+    factor_pipelined(M, Dl, D2, L.Lp, L.T.dof_depth[lane], lane < NH ? L.T.dof_depth[64 + lane] : 0, yl, y2);
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    L.sDinv[lane] = 1.0f / sqrtf(Dl);
+    if (lane < NH) L.sDinv[64 + lane] = 1.0f / sqrtf(D2);
+    // the free velocity is not formed here: the contact bias takes z.u0 + zh.yh, and one L^-1
+    // sweep after the solver gives uf = u0 + L^-1 D^-1/2 (yh + Zh^T lambda)
+    L.yh[lane] = yl * (1.0f / sqrtf(Dl));
+    if (lane < NH) L.yh[64 + lane] = y2 * (1.0f / sqrtf(D2));
+    sync();
+}
+
+// The contact phase's model reads (geometry of the lane's body: body lanes their own geom, corner
+// lanes their box's; the self-collision pair indices of the lane's pairs). They depend on nothing a
+// substep computes: issued after the factorisation, they land behind the free-velocity sweep.
+constexpr int kPairRounds = (HE_MAX_PAIRS + W - 1) / W;
+struct GeomPrefetch {
+    float gv[10];  // geom_params of the lane's geometry body
+    int gt;        // geom_type
+    float grad;    // geom_radius
+    int2 prs[kPairRounds];  // pair rd * W + lane (x = -1: none)
+};
+HE_DEV void prefetch_geometry(const Lds& L, const he_model& m, int lane, GeomPrefetch& g) {
+    const int npairs = m.num_pairs;
+    const int cb = L.T.cbody[lane];
+    const int b = lane < NB ? lane : (cb >= 0 ? cb : 0);
+    const float* gp = m.geom_params[b];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) g.gv[i] = gp[i];
+    g.gt = m.geom_type[b];
+    g.grad = m.geom_radius[b];
+#pragma unroll
+    for (int rd = 0; rd < kPairRounds; ++rd) {
+        const int pi = rd * W + lane;
+        g.prs[rd] = *reinterpret_cast<const int2*>(m.pairs[pi < npairs ? pi : 0]);
+        if (pi >= npairs) g.prs[rd].x = -1;
     }
     sync();
-    STAMP(5);
-    if (!TGS && p.bias_midpoint) bias_midpoint(L, T, lane, p, stamps, t_prev);
-    // the contact phase's model reads (geometry of the lane's body, self-collision pair indices)
-    // depend on nothing computed here: issued now, they land behind the free-velocity sweep
-    constexpr int ROUNDS = (HE_MAX_PAIRS + W - 1) / W;
-    float gv[10];
-    int gt;
-    float grad;
-    int2 prs[ROUNDS];
-    const int npairs = m.num_pairs;
-    {
-        // body lanes their own geom, corner lanes their box's
-        const int cb = L.T.cbody[lane];
-        const int b = lane < NB ? lane : (cb >= 0 ? cb : 0);
-        const float* g = m.geom_params[b];
+}
+
+// ---------------------------------------------------------------------------------- contact slots
+// gen_contacts' reduction scratch in IS (dead after the CRBA): the contact candidates' gaps in
+// candidate order [0, kCand), their bodies (-1: a self pair) [kCand, 2 kCand), the rank order
+// [2 kCand, 3 kCand). After the reduction the last range holds the rows' linear directions (row_dirs,
+// written by row_setup, read by contact_forces_out).
+constexpr int kCand = 128;  // contact candidates considered by the reduction (a lying body: ~30)
+static_assert(3 * kCand <= NG * 6, "reduction scratch fits IS");
+static_assert(2 * kCand + 3 * W <= NG * 6, "per-row force directions fit IS");
+HE_DEV float* cand_gaps(Lds& L) { return &L.IS[0][0]; }
+HE_DEV int* cand_bodies(Lds& L) { return reinterpret_cast<int*>(&L.IS[0][0] + kCand); }
+HE_DEV int* cand_order(Lds& L) { return reinterpret_cast<int*>(&L.IS[0][0] + 2 * kCand); }
+HE_DEV float* row_dirs(Lds& L) { return &L.IS[0][0] + 2 * kCand; }
+
+// joint-angle limit slots (oracle gen_limits), lane = joint b - 1: the rows limit_detect flagged,
+// re-evaluated from the same state words, into slots [0, nlim). Returns nlim; nlim_all counts the
+// flagged joints (past the capacity too).
+HE_DEV int limit_slots(Lds& L, const he_sim_params& p, int lane, int maxc, int& nlim_all) {
+    nlim_all = 0;
+    if (!p.joint_limits) return 0;
+    const uint32_t lm = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.limmask);
+    const bool act = lane < NB - 1 && ((lm >> (lane + 1)) & 1u);
+    const int pre = wave_prefix(act, lane, nlim_all);
+    if (act && pre < maxc) {
+        const int j = lane < NB - 1 ? lane : 0;
+        float lg;
+        f3 ld;
+        angle_row(f3{L.q[3 * j], L.q[3 * j + 1], L.q[3 * j + 2]}, f3{L.u0[6 + 3 * j], L.u0[7 + 3 * j], L.u0[8 + 3 * j]},
+                  p, lg, ld);
+        // the row over the joint's dofs (-q^) travels in the contact position (unused by a limit)
+        store_contact(L, pre, lane + 1, -2, ld * -1.f, f3{0.f, 0.f, 1.f}, lg, row_key(lane + 1, -2, 7, 0));
+    }
+    return nlim_all < maxc ? nlim_all : maxc;
+}
+
+// The lane's terrain candidates: a body lane (lane < 24) takes its sphere's centre or its capsule's
+// end points, a corner lane (lane 24 + 8k + c, he_topo.h corner_body) corner c of the k-th box.
+// Written by terrain_candidates, read by the slot stores of gen_contacts and reduce_overflow.
+static_assert(NB % 8 == 0 && NB + 8 * HE_MAX_BOXES <= W, "corner lanes: 8-lane groups above the body lanes");
+constexpr int kPts = 2;  // terrain points per lane
+struct TerrainLanes {
+    int body;      // the lane's geometry body
+    bool corner;   // a box corner lane
+    int cc;        // its corner index
+    float cd[kPts];         // gap of point ci
+    f3 cxs[kPts], cns[kPts];  // contact point about o, normal
+    bool cand[kPts];        // gap < contact offset
+    int rank[kPts];         // slot offset within the body (8: not kept)
+    int myn, base;          // body lanes: points kept, and the exclusive prefix of them over the bodies
+};
+// Geometry (every lane, of its geometry body):
+//  self segment P0-P1, radius rs: sphere P0 = P1 = centre; capsule from / to; box the capsule
+//    proxy along its longest axis (radius geom_radius)
+//  terrain points, radius rt: sphere the centre; capsule from, to; box corner c around its
+//    centre Pc (world centre +- the world half-axes)
+// Also writes each body's world segment (Ib; TGS: Ic) and bounding sphere (Acc) for self_pairs.
+// Returns the number of terrain candidates kept.
+template <bool TGS>
+HE_DEV int terrain_candidates(Lds& L, const GeomPrefetch& g, const Terrain& ter, float off, bool self_col, int lane,
+                              TerrainLanes& tc, Stamps& st) {
+    const int cbody = L.T.cbody[lane];
+    const bool corner = tc.corner = lane >= NB && cbody >= 0;
+    const int tb_ = tc.body = lane < NB ? lane : (corner ? cbody : 0);
+    const int cc = tc.cc = lane & 7;
+    const f3 ow = f3{L.root_pos[0], L.root_pos[1], L.root_pos[2]};  // points are about o; the terrain is world
+    const bool isS = g.gt == HE_GEOM_SPHERE, isC = g.gt == HE_GEOM_CAPSULE, isB = !isS && !isC;
+    const f4 bq = isB ? f4{g.gv[6], g.gv[7], g.gv[8], g.gv[9]} : f4{0.f, 0.f, 0.f, 1.f};
+    int ax = 0;
+    float emax = g.gv[3];
+    if (g.gv[4] > emax) { ax = 1; emax = g.gv[4]; }
+    if (g.gv[5] > emax) { ax = 2; emax = g.gv[5]; }
+    const float half = fmaxf(emax - g.grad, 0.f);
+    // rotations as matrices (the box's local frame and the body's world rotation): mat-vecs
+    // instead of quaternion applications
+    f3 bc0, bc1, bc2, wc0, wc1, wc2;
+    qcols(bq, bc0, bc1, bc2);
+    qcols(f4{L.qw[tb_][0], L.qw[tb_][1], L.qw[tb_][2], L.qw[tb_][3]}, wc0, wc1, wc2);
+    const f3 pwb = f3{L.pw[tb_][0], L.pw[tb_][1], L.pw[tb_][2]};
+    const f3 dir = (ax == 0 ? bc0 : (ax == 1 ? bc1 : bc2)) * half;
+    const f3 ctr = f3{g.gv[0], g.gv[1], g.gv[2]};
+    const f3 l0 = isB ? ctr - dir : ctr;
+    const f3 l1 = isB ? ctr + dir : (isC ? f3{g.gv[3], g.gv[4], g.gv[5]} : ctr);
+    const float rs = isS ? g.gv[3] : (isC ? g.gv[6] : g.grad);
+    const float rt = isS ? g.gv[3] : (isC ? g.gv[6] : 0.f);
+    auto rot = [&](f3 v) { return (wc0 * v.x + wc1 * v.y) + wc2 * v.z; };
+    const f3 P0 = pwb + rot(l0), P1 = pwb + rot(l1);
+    STAMP(PH_TERRAIN_GEOM);
+    if (self_col && lane < NB) {
+        // world segments (the Ib scratch is dead after the subtree sums), and the bounding
+        // sphere about the segment midpoint for the pair cull as one 16-byte record
+        float* sg = TGS ? L.Ic[lane] : L.Ib[lane];  // TGS: Ib (own inertias) serves the iterations' bias
+        sg[0] = P0.x; sg[1] = P0.y; sg[2] = P0.z; sg[3] = P1.x; sg[4] = P1.y; sg[5] = P1.z; sg[6] = rs;
+        const f3 mid = (P0 + P1) * 0.5f;
+        bsph(L)[lane] = make_float4(mid.x, mid.y, mid.z, 0.5f * norm3(P1 - P0) + rs);
+    }
+    // a corner lane's point: ((Pc +- ex) +- ey) +- ez, signs by the bits of c
+    f3 X0 = P0;
+    if (corner) {
+        const f3 Pc = pwb + rot(ctr);
+        const f3 ex = rot(bc0 * g.gv[3]), ey = rot(bc1 * g.gv[4]), ez = rot(bc2 * g.gv[5]);
+        X0 = ((Pc + ((cc & 1) ? ex : ex * -1.f)) + ((cc & 2) ? ey : ey * -1.f)) + ((cc & 4) ? ez : ez * -1.f);
+    }
+    const int npts = lane < NB ? (isS ? 1 : (isC ? 2 : 0)) : (corner ? 1 : 0);
 #pragma unroll
-        for (int i = 0; i < 10; ++i) gv[i] = g[i];
-        gt = m.geom_type[b];
-        grad = m.geom_radius[b];
+    for (int ci = 0; ci < kPts; ++ci) {
+        const f3 x = ci == 0 ? X0 : P1;
+        tc.cd[ci] = terrain_dist(ter, ow + x, tc.cns[ci]) - rt;
+        tc.cxs[ci] = x - tc.cns[ci] * rt;
+        tc.cand[ci] = ci < npts && tc.cd[ci] < off;
+    }
+    // a box keeps its 4 deepest corners (ties by index): a corner lane's rank among the 8 lanes
+    // of its group, keys through xor swizzles (non-candidates keyed +inf never go first)
+    const float key = corner && tc.cand[0] ? tc.cd[0] : __builtin_inff();
+    int r = 0;
+    auto beat = [&](float kj, int sx) { r += (kj < key || (kj == key && (cc ^ sx) < cc)) ? 1 : 0; };
+    beat(swizzle_xor<1>(key), 1);
+    beat(swizzle_xor<2>(key), 2);
+    beat(swizzle_xor<3>(key), 3);
+    beat(swizzle_xor<4>(key), 4);
+    beat(swizzle_xor<5>(key), 5);
+    beat(swizzle_xor<6>(key), 6);
+    beat(swizzle_xor<7>(key), 7);
+    const bool kept0 = tc.cand[0] && (!corner || r < 4), kept1 = tc.cand[1];
+    // the kept points take the body's slots in point index order (box corners by corner index),
+    // so that resting contacts keep their slots from one substep to the next (the warm start then
+    // maps impulses one to one); rank[] becomes that slot offset within the body
+    const uint64_t kb = __ballot(corner && kept0);
+    const uint64_t bxm = __ballot(lane < NB && isB);
+    const int kbox = ballot_below(bxm);
+    const uint32_t grp = (uint32_t)(kb >> (corner ? (lane & ~7) : (NB + 8 * (kbox < HE_MAX_BOXES ? kbox : 0)))) & 0xFFu;
+    tc.myn = lane < NB ? (isB ? __popc(grp) : (kept0 ? 1 : 0) + (kept1 ? 1 : 0)) : 0;
+    int total;
+    tc.base = wave_prefix3(tc.myn, total);  // over the body lanes (myn = 0 elsewhere)
+    // a corner lane starts from its box body's base
+    const int bbase = __builtin_amdgcn_ds_bpermute(4 * tb_, tc.base);
+    if (corner) tc.base = bbase;
+    tc.rank[0] = kept0 ? (corner ? __popc(grp & ((1u << cc) - 1u)) : 0) : 8;
+    tc.rank[1] = kept1 ? (kept0 ? 1 : 0) : 8;
+    return total;
+}
+
+// The terrain slot store: each kept point (candidate k = base + rank, in slot order) into slot(k)
+// when keep(k). RECORD: also its gap and body for the reduction. The contact key's sub-index is the
+// point's index on its body (a box's corner index).
+template <bool RECORD, class Keep, class Slot>
+HE_DEV void store_terrain_slots(Lds& L, const TerrainLanes& tc, Keep keep, Slot slot) {
 #pragma unroll
-        for (int rd = 0; rd < ROUNDS; ++rd) {
-            const int pi = rd * W + lane;
-            prs[rd] = *reinterpret_cast<const int2*>(m.pairs[pi < npairs ? pi : 0]);
-            if (pi >= npairs) prs[rd].x = -1;
+    for (int ci = 0; ci < kPts; ++ci) {
+        if (tc.cand[ci] && tc.rank[ci] < 4) {
+            const int k = tc.base + tc.rank[ci];
+            if constexpr (RECORD) {
+                if (k < kCand) { cand_gaps(L)[k] = tc.cd[ci]; cand_bodies(L)[k] = tc.body; }
+            }
+            if (keep(k))
+                store_contact(L, slot(k), tc.body, -1, tc.cxs[ci], tc.cns[ci], tc.cd[ci],
+                              row_key(tc.body, -1, tc.corner ? tc.cc : ci, 0));
+        }
+    }
+}
+
+// Self pairs (oracle gen_contacts, the pair loop): broad phase (bounding spheres, survivors compacted
+// in pair order into the lam scratch: lam's impulses must have been read), narrow phase W survivors
+// per pass; `visit(hit, i, j, x, n, gap, k)` gets every hit with its candidate index k (in pair order
+// after the terr_all terrain candidates). Reads the segments and spheres terrain_candidates wrote.
+// Returns the hits.
+template <bool TGS, class Visit>
+HE_DEV int self_pairs(Lds& L, const GeomPrefetch& g, float off, int terr_all, int lane, Stamps& st, Visit visit) {
+    sync();
+    int* list = reinterpret_cast<int*>(L.lam);
+    auto compact = [&](int skip) {  // survivors skip .. skip + W - 1 into the list
+        int k = 0;
+#pragma unroll
+        for (int rd = 0; rd < kPairRounds; ++rd) {
+            const int i = g.prs[rd].x, j = g.prs[rd].y;
+            bool need = false;
+            if (i >= 0) {
+                const float4 bi = bsph(L)[i], bj = bsph(L)[j];
+                const f3 d = f3{bi.x - bj.x, bi.y - bj.y, bi.z - bj.z};
+                const float lim = bi.w + bj.w + off + 1e-3f;
+                need = dot3(d, d) < lim * lim;
+            }
+            const uint64_t bm = __ballot(need);
+            const int slot = k + ballot_below(bm) - skip;
+            if (need && slot >= 0 && slot < W) list[slot] = (rd * W + lane) | (i << 16) | (j << 24);
+            k += __popcll(bm);
+        }
+        sync();
+        return k;
+    };
+    // broad phase: a pair whose bounding spheres (segment midpoint, half length + radius) are
+    // apart by more than the contact offset plus a 1 mm guard cannot reach gap < offset
+    const int nsurv = compact(0);
+    STAMP(PH_SELF_SEGMENTS);
+    int nhit = 0;
+    for (int s0 = 0; s0 < nsurv; s0 += W) {
+        bool hit = false;
+        f3 px = f3{0.f, 0.f, 0.f}, pn = f3{0.f, 0.f, 0.f};
+        float pgap = 0.f;
+        int i = 0, j = 0;
+        if (s0 + lane < nsurv) {
+            const int e = list[lane];
+            i = (e >> 16) & 0xFF;
+            j = (e >> 24) & 0xFF;
+            const float* si = TGS ? L.Ic[i] : L.Ib[i];
+            const float* sj = TGS ? L.Ic[j] : L.Ib[j];
+            const float ri = si[6], rj = sj[6];
+            f3 ci, cj;
+            seg_seg(f3{si[0], si[1], si[2]}, f3{si[3], si[4], si[5]}, f3{sj[0], sj[1], sj[2]}, f3{sj[3], sj[4], sj[5]}, ci, cj);
+            const f3 dv = ci - cj;
+            const float len = norm3(dv);
+            pgap = len - ri - rj;
+            if (pgap < off) {
+                hit = true;
+                pn = len > 1e-9f ? dv * __builtin_amdgcn_rcpf(len) : f3{0.f, 0.f, 1.f};
+                px = cj + pn * (rj + 0.5f * pgap);
+            }
+        }
+        int total;
+        const int pre = wave_prefix(hit, lane, total);
+        visit(hit, i, j, px, pn, pgap, terr_all + nhit + pre);
+        nhit += total;
+        if (s0 + W < nsurv) compact(s0 + W);  // more than W survivors: the next pass (rare)
+    }
+    return nhit;
+}
+
+// Overflow (rare, wave-uniform): the candidates are past the slots or the solver rows. The contacts
+// are taken deepest first (smallest gap, ties in slot order), each kept while its rows still fit (a
+// self pair or a body's first terrain point 3, its second 2, 1 after: oracle gen_contacts), and the
+// kept ones are regenerated in slot order. Reads the gaps and bodies gen_contacts recorded (IS), uses
+// the rank order's words. Returns the contact slots in use.
+template <bool TGS>
+HE_DEV int reduce_overflow(Lds& L, const GeomPrefetch& g, const Terrain& ter, float off, bool self_col, int lane, int maxc,
+                           int nlim, int terr_all, int self_all, TerrainLanes& tc, Stamps& st) {
+    const float* gl = cand_gaps(L);
+    int *gb = cand_bodies(L), *gord = cand_order(L);
+    sync();
+    const int keep = maxc - nlim;
+    const int T = terr_all + self_all < kCand ? terr_all + self_all : kCand;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {  // each candidate's depth rank -> the rank order
+        const int k = h * W + lane;
+        if (k < T) {
+            const float gk = gl[k];
+            int r = 0;
+            for (int jj = 0; jj < T; ++jj) {  // uniform LDS reads (broadcast)
+                const float g2 = gl[jj];
+                r += (g2 < gk || (g2 == gk && jj < k)) ? 1 : 0;
+            }
+            gord[r] = k;
         }
     }
     sync();
-    STAMP(6);
-    // ---- contact slots: joint limits, terrain (bodies in order, box corners deepest-first), self
-    // pairs (oracle/he_oracle_physics.c gen_contacts). Every contact generated is counted; when
-    // they exceed the capacity, the limits stay and the contacts are reduced to the deepest ones
-    // (smallest gap, ties in slot order), kept in slot order. The gap of each contact candidate is
-    // recorded in candidate order in the IS scratch (dead after the CRBA) for that reduction.
+    // the greedy pass in rank order (wave-uniform): candidate and body from registers by
+    // v_readlane, the kept points per body in lane = body
+    const int ko0 = lane < T ? gord[lane] : 0, ko1 = W + lane < T ? gord[W + lane < kCand ? W + lane : 0] : 0;
+    const int kb0 = gb[ko0], kb1 = gb[ko1];
+    uint64_t km[2] = {0ull, 0ull};
+    int rows = nlim, kept_n = 0, pcnt = 0;
+    for (int q = 0; q < T; ++q) {
+        const int k = q < W ? __builtin_amdgcn_readlane(ko0, q & (W - 1)) : __builtin_amdgcn_readlane(ko1, q & (W - 1));
+        const int b = q < W ? __builtin_amdgcn_readlane(kb0, q & (W - 1)) : __builtin_amdgcn_readlane(kb1, q & (W - 1));
+        const int pc = b >= 0 ? __builtin_amdgcn_readlane(pcnt, b) : 0;
+        const int cost = b < 0 ? 3 : (pc == 0 ? 3 : (pc == 1 ? 2 : 1));
+        if (kept_n < keep && rows + cost <= MAXR) {
+            rows += cost;
+            ++kept_n;
+            pcnt += lane == b ? 1 : 0;
+            if (k < W) km[0] |= 1ull << (k & (W - 1));
+            else km[1] |= 1ull << (k & (W - 1));
+        }
+    }
+    auto before = [&](int k) {  // kept candidates below index k
+        const uint64_t lo = k >= W ? km[0] : (k <= 0 ? 0ull : km[0] & ((~0ull) >> (W - k)));
+        const uint64_t hi = k <= W ? 0ull : (k >= 2 * W ? km[1] : km[1] & ((~0ull) >> (2 * W - k)));
+        return __popcll(lo) + __popcll(hi);
+    };
+    auto is_kept = [&](int k) { return k < 2 * W && ((km[k >= W ? 1 : 0] >> (k & (W - 1))) & 1ull); };
+    terrain_candidates<TGS>(L, g, ter, off, self_col, lane, tc, st);
+    store_terrain_slots<false>(L, tc, is_kept, [&](int k) { return nlim + before(k); });
+    if (lane < NB) {
+        const int s0 = nlim + before(tc.base);
+        L.tbase[lane] = (int8_t)s0;
+        L.tcnt[lane] = (int8_t)(nlim + before(tc.base + tc.myn) - s0);
+    }
+    if (lane == 0) L.nterr = nlim + before(terr_all);
+    if (self_col) {
+        self_pairs<TGS>(L, g, off, terr_all, lane, st, [&](bool hit, int i, int j, f3 px, f3 pn, float pgap, int k) {
+            if (hit && is_kept(k)) store_contact(L, nlim + before(k), i, j, px, pn, pgap, row_key(i, j, 0, 0));
+        });
+    }
+    return nlim + before(T);
+}
+
+// Contact slots (oracle gen_contacts): joint limits, terrain (bodies in order, box corners
+// deepest-first), self pairs. Every contact generated is counted; when they exceed the capacity, the
+// limits stay and the contacts are reduced to the deepest ones, kept in slot order (reduce_overflow).
+// Writes the slots (cx, cn, cgap, cbb, ckey), tbase / tcnt, nc, nterr, nlim, ncand, and zeroes cf.
+// Scratch: IS (candidate records), lam (pair list), Ib / Ic (segments), Acc (bounding spheres).
+// Returns the contact slots in use.
+template <bool TGS>
+HE_DEV int gen_contacts(Lds& L, const GeomPrefetch& g, const he_sim_params& p, int tkind, int lane, Stamps& st) {
     const int maxc = p.max_contacts < MAXC ? p.max_contacts : MAXC;
     const float off = p.contact_offset;
     const Terrain ter = terrain_of(p, tkind);
     const bool self_col = p.self_collision;
-    float* gl = &L.IS[0][0];
-    constexpr int kCand = 128;  // contact candidates considered by the reduction (a lying body: ~30)
-    static_assert(kCand <= NG * 6, "candidate gaps fit the IS scratch");
-    // the previous solve's impulses (lane = row) before the self-pair list reuses L.lam as scratch
-    const float lam_prev = L.lam[lane];
-    // -- joint-angle limit slots (lane = joint b - 1): the rows limit_detect flagged, re-evaluated
-    // from the same state words
-    int nlim = 0, nlim_all = 0;
-    if (p.joint_limits) {
-        const uint32_t lm = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.limmask);
-        const bool act = lane < NB - 1 && ((lm >> (lane + 1)) & 1u);
-        const int pre = wave_prefix(act, lane, nlim_all);
-        if (act && pre < maxc) {
-            const int j = lane < NB - 1 ? lane : 0;
-            float lg;
-            f3 ld;
-            angle_row(f3{L.q[3 * j], L.q[3 * j + 1], L.q[3 * j + 2]}, f3{L.u0[6 + 3 * j], L.u0[7 + 3 * j], L.u0[8 + 3 * j]},
-                      p, lg, ld);
-            // the row over the joint's dofs (-q^) travels in the contact position (unused by a limit)
-            store_contact(L, pre, lane + 1, -2, ld * -1.f, f3{0.f, 0.f, 1.f}, lg, row_key(lane + 1, -2, 7, 0));
-        }
-        nlim = nlim_all < maxc ? nlim_all : maxc;
+    int nlim_all = 0;
+    const int nlim = limit_slots(L, p, lane, maxc, nlim_all);
+    STAMP(PH_LIMIT_SLOTS);
+    TerrainLanes tc;
+    const int terr_all = terrain_candidates<TGS>(L, g, ter, off, self_col, lane, tc, st);
+    STAMP(PH_TERRAIN_RANK);
+    store_terrain_slots<true>(L, tc, [&](int k) { return nlim + k < maxc; }, [&](int k) { return nlim + k; });
+    // rows of the body's patch: k points, k normal rows + 2 tangential (+ 1 torsional from k = 2)
+    int rows_terr;  // solver rows of every terrain candidate kept (patch friction)
+    wave_prefix3(tc.myn == 0 ? 0 : tc.myn + (tc.myn >= 2 ? 3 : 2), rows_terr);
+    int nc = nlim + terr_all < maxc ? nlim + terr_all : maxc, self_all = 0;
+    if (lane < NB) {  // the body's slot range, for the per-body force sums
+        const int s0 = nlim + tc.base;
+        L.tbase[lane] = (int8_t)(s0 < maxc ? s0 : maxc);
+        L.tcnt[lane] = (int8_t)(s0 + tc.myn < maxc ? tc.myn : (s0 < maxc ? maxc - s0 : 0));
     }
-    int nc = nlim;
-    int terr_all = 0, self_all = 0;
-    STAMP(14);
-    // -- terrain candidates, one per lane-slot: a body lane (lane < 24) takes its sphere's centre or
-    // its capsule's end points, a corner lane (lane 24 + 8k + c, he_topo.h corner_body) corner c of
-    // the k-th box. Geometry (every lane, of its geometry body tb_):
-    //  self segment P0-P1, radius rs: sphere P0 = P1 = centre; capsule from / to; box the capsule
-    //    proxy along its longest axis (radius geom_radius)
-    //  terrain points, radius rt: sphere the centre; capsule from, to; box corner c around its
-    //    centre Pc (world centre +- the world half-axes)
-    static_assert(NB % 8 == 0 && NB + 8 * HE_MAX_BOXES <= W, "corner lanes: 8-lane groups above the body lanes");
-    constexpr int kPts = 2;  // terrain points per lane
-    const int cbody = L.T.cbody[lane];
-    const bool corner = lane >= NB && cbody >= 0;
-    const int tb_ = lane < NB ? lane : (corner ? cbody : 0);
-    const int cc = lane & 7;  // a corner lane's corner index
-    const f3 ow = f3{L.root_pos[0], L.root_pos[1], L.root_pos[2]};  // points are about o; the terrain is world
-    const bool isS = gt == HE_GEOM_SPHERE, isC = gt == HE_GEOM_CAPSULE, isB = !isS && !isC;
-    float cd[kPts];
-    f3 cxs[kPts], cns[kPts];
-    bool cand[kPts];
-    int rank[kPts];
-    int myn = 0, base = 0;
-    auto terrain_candidates = [&]() {
-        const f4 bq = isB ? f4{gv[6], gv[7], gv[8], gv[9]} : f4{0.f, 0.f, 0.f, 1.f};
-        int ax = 0;
-        float emax = gv[3];
-        if (gv[4] > emax) { ax = 1; emax = gv[4]; }
-        if (gv[5] > emax) { ax = 2; emax = gv[5]; }
-        const float half = fmaxf(emax - grad, 0.f);
-        // rotations as matrices (the box's local frame and the body's world rotation): mat-vecs
-        // instead of quaternion applications
-        f3 bc0, bc1, bc2, wc0, wc1, wc2;
-        qcols(bq, bc0, bc1, bc2);
-        qcols(f4{L.qw[tb_][0], L.qw[tb_][1], L.qw[tb_][2], L.qw[tb_][3]}, wc0, wc1, wc2);
-        const f3 pwb = f3{L.pw[tb_][0], L.pw[tb_][1], L.pw[tb_][2]};
-        const f3 dir = (ax == 0 ? bc0 : (ax == 1 ? bc1 : bc2)) * half;
-        const f3 ctr = f3{gv[0], gv[1], gv[2]};
-        const f3 l0 = isB ? ctr - dir : ctr;
-        const f3 l1 = isB ? ctr + dir : (isC ? f3{gv[3], gv[4], gv[5]} : ctr);
-        const float rs = isS ? gv[3] : (isC ? gv[6] : grad);
-        const float rt = isS ? gv[3] : (isC ? gv[6] : 0.f);
-        auto rot = [&](f3 v) { return (wc0 * v.x + wc1 * v.y) + wc2 * v.z; };
-        const f3 P0 = pwb + rot(l0), P1 = pwb + rot(l1);
-        STAMP(18);
-        if (self_col && lane < NB) {
-            // world segments (the Ib scratch is dead after the subtree sums), and the bounding
-            // sphere about the segment midpoint for the pair cull as one 16-byte record
-            float* sg = TGS ? L.Ic[lane] : L.Ib[lane];  // TGS: Ib (own inertias) serves the iterations' bias
-            sg[0] = P0.x; sg[1] = P0.y; sg[2] = P0.z; sg[3] = P1.x; sg[4] = P1.y; sg[5] = P1.z; sg[6] = rs;
-            const f3 mid = (P0 + P1) * 0.5f;
-            bsph(L)[lane] = make_float4(mid.x, mid.y, mid.z, 0.5f * norm3(P1 - P0) + rs);
-        }
-        // a corner lane's point: ((Pc +- ex) +- ey) +- ez, signs by the bits of c
-        f3 X0 = P0;
-        if (corner) {
-            const f3 Pc = pwb + rot(ctr);
-            const f3 ex = rot(bc0 * gv[3]), ey = rot(bc1 * gv[4]), ez = rot(bc2 * gv[5]);
-            X0 = ((Pc + ((cc & 1) ? ex : ex * -1.f)) + ((cc & 2) ? ey : ey * -1.f)) + ((cc & 4) ? ez : ez * -1.f);
-        }
-        const int npts = lane < NB ? (isS ? 1 : (isC ? 2 : 0)) : (corner ? 1 : 0);
-#pragma unroll
-        for (int ci = 0; ci < kPts; ++ci) {
-            const f3 x = ci == 0 ? X0 : P1;
-            cd[ci] = terrain_dist(ter, ow + x, cns[ci]) - rt;
-            cxs[ci] = x - cns[ci] * rt;
-            cand[ci] = ci < npts && cd[ci] < off;
-        }
-        // a box keeps its 4 deepest corners (ties by index): a corner lane's rank among the 8 lanes
-        // of its group, keys through xor swizzles (non-candidates keyed +inf never go first)
-        const float key = corner && cand[0] ? cd[0] : __builtin_inff();
-        int r = 0;
-        auto beat = [&](float kj, int sx) { r += (kj < key || (kj == key && (cc ^ sx) < cc)) ? 1 : 0; };
-        beat(swizzle_xor<1>(key), 1);
-        beat(swizzle_xor<2>(key), 2);
-        beat(swizzle_xor<3>(key), 3);
-        beat(swizzle_xor<4>(key), 4);
-        beat(swizzle_xor<5>(key), 5);
-        beat(swizzle_xor<6>(key), 6);
-        beat(swizzle_xor<7>(key), 7);
-        const bool kept0 = cand[0] && (!corner || r < 4), kept1 = cand[1];
-        // the kept points take the body's slots in point index order (box corners by corner index),
-        // so that resting contacts keep their slots from one substep to the next (the warm start then
-        // maps impulses one to one); rank[] becomes that slot offset within the body
-        const uint64_t kb = __ballot(corner && kept0);
-        const uint64_t bxm = __ballot(lane < NB && isB);
-        const int kbox = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bxm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bxm, 0u));
-        const uint32_t grp = (uint32_t)(kb >> (corner ? (lane & ~7) : (NB + 8 * (kbox < HE_MAX_BOXES ? kbox : 0)))) & 0xFFu;
-        myn = lane < NB ? (isB ? __popc(grp) : (kept0 ? 1 : 0) + (kept1 ? 1 : 0)) : 0;
-        // exclusive prefix of myn (0..4) over the body lanes: three bit ballots, v_mbcnt per bit
-        base = 0;
-        int total = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t bm = __ballot((myn >> k) & 1);
-            base += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) << k;
-            total += __popcll(bm) << k;
-        }
-        // a corner lane starts from its box body's base
-        const int bbase = __builtin_amdgcn_ds_bpermute(4 * tb_, base);
-        if (corner) base = bbase;
-        rank[0] = kept0 ? (corner ? __popc(grp & ((1u << cc) - 1u)) : 0) : 8;
-        rank[1] = kept1 ? (kept0 ? 1 : 0) : 8;
-        return total;
-    };
-    // the contact key's sub-index: the point's index on its body (a box's corner index)
-    auto sub_of = [&](int ci) { return corner ? cc : ci; };
-    // candidate gaps and bodies for the reduction (IS scratch: gaps [0, kCand), bodies (-1: a self
-    // pair) [kCand, 2 kCand), the rank order [2 kCand, 3 kCand))
-    int* gb = reinterpret_cast<int*>(gl + kCand);
-    int* gord = reinterpret_cast<int*>(gl + 2 * kCand);
-    static_assert(3 * kCand <= NG * 6, "reduction scratch fits IS");
-    int rows_terr = 0;  // solver rows of every terrain candidate kept (patch friction)
-    {
-        terr_all = terrain_candidates();
-        STAMP(16);
-        // candidate k = base + rank (in slot order): its gap for the reduction, its slot nlim + k
-#pragma unroll
-        for (int ci = 0; ci < kPts; ++ci) {
-            if (cand[ci] && rank[ci] < 4) {
-                const int k = base + rank[ci];
-                if (k < kCand) { gl[k] = cd[ci]; gb[k] = tb_; }
-                if (nlim + k < maxc)
-                    store_contact(L, nlim + k, tb_, -1, cxs[ci], cns[ci], cd[ci], row_key(tb_, -1, sub_of(ci), 0));
-            }
-        }
-        // rows of the body's patch: k points, k normal rows + 2 tangential (+ 1 torsional from k = 2)
-        const int pr = myn == 0 ? 0 : myn + (myn >= 2 ? 3 : 2);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rows_terr += __popcll(__ballot((pr >> k) & 1)) << k;
-        nc = nlim + terr_all < maxc ? nlim + terr_all : maxc;
-        if (lane < NB) {  // the body's slot range, for the per-body force sums
-            const int s0 = nlim + base;
-            L.tbase[lane] = (int8_t)(s0 < maxc ? s0 : maxc);
-            L.tcnt[lane] = (int8_t)(s0 + myn < maxc ? myn : (s0 < maxc ? maxc - s0 : 0));
-        }
-        if (lane == 0) L.nterr = nc;
-    }
-    STAMP(17);
-    // -- self pairs: broad phase (bounding spheres, survivors compacted in pair order into the lam
-    // scratch), narrow phase W survivors per pass; `visit(hit, i, j, x, n, gap, k)` gets every hit
-    // with its candidate index k (in pair order after the terrain candidates)
-    auto self_pairs = [&](auto visit) {
-        sync();
-        int* list = reinterpret_cast<int*>(L.lam);
-        auto compact = [&](int skip) {  // survivors skip .. skip + W - 1 into the list
-            int k = 0;
-#pragma unroll
-            for (int rd = 0; rd < ROUNDS; ++rd) {
-                const int i = prs[rd].x, j = prs[rd].y;
-                bool need = false;
-                if (i >= 0) {
-                    const float4 bi = bsph(L)[i], bj = bsph(L)[j];
-                    const f3 d = f3{bi.x - bj.x, bi.y - bj.y, bi.z - bj.z};
-                    const float lim = bi.w + bj.w + off + 1e-3f;
-                    need = dot3(d, d) < lim * lim;
-                }
-                const uint64_t bm = __ballot(need);
-                const int slot = k + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) - skip;
-                if (need && slot >= 0 && slot < W) list[slot] = (rd * W + lane) | (i << 16) | (j << 24);
-                k += __popcll(bm);
-            }
-            sync();
-            return k;
-        };
-        // broad phase: a pair whose bounding spheres (segment midpoint, half length + radius) are
-        // apart by more than the contact offset plus a 1 mm guard cannot reach gap < offset
-        const int nsurv = compact(0);
-        STAMP(19);
-        int nhit = 0;
-        for (int s0 = 0; s0 < nsurv; s0 += W) {
-            bool hit = false;
-            f3 px = f3{0.f, 0.f, 0.f}, pn = f3{0.f, 0.f, 0.f};
-            float pgap = 0.f;
-            int i = 0, j = 0;
-            if (s0 + lane < nsurv) {
-                const int e = list[lane];
-                i = (e >> 16) & 0xFF;
-                j = (e >> 24) & 0xFF;
-                const float* si = TGS ? L.Ic[i] : L.Ib[i];
-                const float* sj = TGS ? L.Ic[j] : L.Ib[j];
-                const float ri = si[6], rj = sj[6];
-                f3 ci, cj;
-                seg_seg(f3{si[0], si[1], si[2]}, f3{si[3], si[4], si[5]}, f3{sj[0], sj[1], sj[2]}, f3{sj[3], sj[4], sj[5]}, ci, cj);
-                const f3 dv = ci - cj;
-                const float len = norm3(dv);
-                pgap = len - ri - rj;
-                if (pgap < off) {
-                    hit = true;
-                    pn = len > 1e-9f ? dv * __builtin_amdgcn_rcpf(len) : f3{0.f, 0.f, 1.f};
-                    px = cj + pn * (rj + 0.5f * pgap);
-                }
-            }
-            int total;
-            const int pre = wave_prefix(hit, lane, total);
-            visit(hit, i, j, px, pn, pgap, terr_all + nhit + pre);
-            nhit += total;
-            if (s0 + W < nsurv) compact(s0 + W);  // more than W survivors: the next pass (rare)
-        }
-        return nhit;
-    };
+    if (lane == 0) L.nterr = nc;
+    STAMP(PH_TERRAIN_SLOTS);
     if (self_col) {
-        self_all = self_pairs([&](bool hit, int i, int j, f3 px, f3 pn, float pgap, int k) {
-            if (hit && k < kCand) { gl[k] = pgap; gb[k] = -1; }
+        self_all = self_pairs<TGS>(L, g, off, terr_all, lane, st, [&](bool hit, int i, int j, f3 px, f3 pn, float pgap, int k) {
+            if (hit && k < kCand) { cand_gaps(L)[k] = pgap; cand_bodies(L)[k] = -1; }
             if (hit && nlim + k < maxc) store_contact(L, nlim + k, i, j, px, pn, pgap, row_key(i, j, 0, 0));
         });
         nc = nlim + terr_all + self_all < maxc ? nlim + terr_all + self_all : maxc;
     }
     const int ncand_all = nlim_all + terr_all + self_all;
-    if ((nlim + terr_all + self_all > maxc || nlim + rows_terr + 3 * self_all > MAXR) && nlim < maxc) {
-        // ---- overflow (rare, wave-uniform): past the slots or the solver rows. The contacts are
-        // taken deepest first (smallest gap, ties in slot order), each kept while its rows still fit
-        // (a self pair or a body's first terrain point 3, its second 2, 1 after: oracle gen_contacts),
-        // and the kept ones are regenerated in slot order
-        sync();
-        const int keep = maxc - nlim;
-        const int T = terr_all + self_all < kCand ? terr_all + self_all : kCand;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {  // each candidate's depth rank -> the rank order
-            const int k = h * W + lane;
-            if (k < T) {
-                const float gk = gl[k];
-                int r = 0;
-                for (int jj = 0; jj < T; ++jj) {  // uniform LDS reads (broadcast)
-                    const float g2 = gl[jj];
-                    r += (g2 < gk || (g2 == gk && jj < k)) ? 1 : 0;
-                }
-                gord[r] = k;
-            }
-        }
-        sync();
-        // the greedy pass in rank order (wave-uniform): candidate and body from registers by
-        // v_readlane, the kept points per body in lane = body
-        const int ko0 = lane < T ? gord[lane] : 0, ko1 = W + lane < T ? gord[W + lane < kCand ? W + lane : 0] : 0;
-        const int kb0 = gb[ko0], kb1 = gb[ko1];
-        uint64_t km[2] = {0ull, 0ull};
-        int rows = nlim, kept_n = 0, pcnt = 0;
-        for (int q = 0; q < T; ++q) {
-            const int k = q < W ? __builtin_amdgcn_readlane(ko0, q & (W - 1)) : __builtin_amdgcn_readlane(ko1, q & (W - 1));
-            const int b = q < W ? __builtin_amdgcn_readlane(kb0, q & (W - 1)) : __builtin_amdgcn_readlane(kb1, q & (W - 1));
-            const int pc = b >= 0 ? __builtin_amdgcn_readlane(pcnt, b) : 0;
-            const int cost = b < 0 ? 3 : (pc == 0 ? 3 : (pc == 1 ? 2 : 1));
-            if (kept_n < keep && rows + cost <= MAXR) {
-                rows += cost;
-                ++kept_n;
-                pcnt += lane == b ? 1 : 0;
-                if (k < W) km[0] |= 1ull << (k & (W - 1));
-                else km[1] |= 1ull << (k & (W - 1));
-            }
-        }
-        auto before = [&](int k) {  // kept candidates below index k
-            const uint64_t lo = k >= W ? km[0] : (k <= 0 ? 0ull : km[0] & ((~0ull) >> (W - k)));
-            const uint64_t hi = k <= W ? 0ull : (k >= 2 * W ? km[1] : km[1] & ((~0ull) >> (2 * W - k)));
-            return __popcll(lo) + __popcll(hi);
-        };
-        auto is_kept = [&](int k) { return k < 2 * W && ((km[k >= W ? 1 : 0] >> (k & (W - 1))) & 1ull); };
-        terrain_candidates();
-#pragma unroll
-        for (int ci = 0; ci < kPts; ++ci) {
-            if (cand[ci] && rank[ci] < 4) {
-                const int k = base + rank[ci];
-                if (is_kept(k))
-                    store_contact(L, nlim + before(k), tb_, -1, cxs[ci], cns[ci], cd[ci], row_key(tb_, -1, sub_of(ci), 0));
-            }
-        }
-        if (lane < NB) {
-            const int s0 = nlim + before(base);
-            L.tbase[lane] = (int8_t)s0;
-            L.tcnt[lane] = (int8_t)(nlim + before(base + myn) - s0);
-        }
-        if (lane == 0) L.nterr = nlim + before(terr_all);
-        if (self_col) {
-            self_pairs([&](bool hit, int i, int j, f3 px, f3 pn, float pgap, int k) {
-                if (hit && is_kept(k)) store_contact(L, nlim + before(k), i, j, px, pn, pgap, row_key(i, j, 0, 0));
-            });
-        }
-        nc = nlim + before(T);
-    }
-    STAMP(15);
+    if ((nlim + terr_all + self_all > maxc || nlim + rows_terr + 3 * self_all > MAXR) && nlim < maxc)
+        nc = reduce_overflow<TGS>(L, g, ter, off, self_col, lane, maxc, nlim, terr_all, self_all, tc, st);
+    STAMP(PH_SELF_SLOTS);
     if (lane == 0) { L.nc = nc; L.nlim = nlim; L.ncand = ncand_all; }
     if (lane < NB) { L.cf[lane][0] = 0.f; L.cf[lane][1] = 0.f; L.cf[lane][2] = 0.f; }
     sync();
-    // ---- solver rows (patch friction, oracle build_rows), lane = slot: a joint limit 1 row, a point
-    // its normal row, the last point of a body's terrain patch then the patch's 2 tangential rows
-    // (+ 1 torsional from 2 points on), a self pair its normal and 2 tangential rows; the row table
-    // (row -> slot, kind) by the slots' exclusive prefix
+    return nc;
+}
+
+// ---------------------------------------------------------------------------------- solver rows
+// build_rows' patch radii: the Acc words after the bounding spheres (read by row_setup)
+HE_DEV float* patch_radius(Lds& L) { return &L.Acc[0][0] + 4 * NB; }
+static_assert(5 * NB <= 6 * NB, "patch radii fit Acc after the bounding spheres");
+
+// Solver rows (patch friction, oracle build_rows), lane = slot: a joint limit 1 row, a point its
+// normal row, the last point of a body's terrain patch then the patch's 2 tangential rows (+ 1
+// torsional from 2 points on), a self pair its normal and 2 tangential rows; the row table (srow0,
+// rslot, rkind) by the slots' exclusive prefix. Then each body's terrain patch (lane = body, tcnt >
+// 0): normal = the normalised sum of its points' normals, the points' centroid (about o) and the
+// torsion radius (mean tangential distance of the points from the centroid), into the RNEA force
+// scratch F (dead from the midpoint bias to the next substep's force pass) and patch_radius.
+// Returns the number of rows.
+HE_DEV int build_rows(Lds& L, int lane, int nc) {
     int nr = 0;
     {
         const bool on = lane < nc;
@@ -2076,13 +1966,7 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
                 cost = lane == L.tbase[b0] + tn - 1 ? 1 + (tn >= 2 ? 3 : 2) : 1;
             }
         }
-        int start = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t bm = __ballot((cost >> k) & 1);
-            start += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) << k;
-            nr += __popcll(bm) << k;
-        }
+        const int start = wave_prefix3(cost, nr);
         if (on) {
             L.srow0[lane < MAXC ? lane : 0] = (int8_t)start;
 #pragma unroll
@@ -2090,12 +1974,6 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
                 if (k < cost) { L.rslot[start + k] = (int8_t)lane; L.rkind[start + k] = (int8_t)k; }
         }
     }
-    // ---- each body's terrain patch (lane = body, tcnt > 0): normal = the normalised sum of its
-    // points' normals, the points' centroid (about o) and the torsion radius (mean tangential
-    // distance of the points from the centroid), into the RNEA force scratch F (dead from the
-    // midpoint bias to the next substep's force pass) and the Acc words after the bounding spheres
-    float* prad = &L.Acc[0][0] + 4 * NB;
-    static_assert(5 * NB <= 6 * NB, "patch radii fit Acc after the bounding spheres");
     if (lane < NB && L.tcnt[lane] > 0) {
         const int p0 = L.tbase[lane], pc = L.tcnt[lane];
         f3 px[4];
@@ -2120,34 +1998,49 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
         }
         float* pf = L.F[lane];
         pf[0] = np.x; pf[1] = np.y; pf[2] = np.z; pf[3] = xp.x; pf[4] = xp.y; pf[5] = xp.z;
-        prad[lane] = rp * (1.0f / (float)pc);
+        patch_radius(L)[lane] = rp * (1.0f / (float)pc);
     }
     sync();
-    STAMP(7);
-    // ---- each row's Jacobian data (lane = row): slot, kind, bodies; a friction row's patch (a
-    // body's terrain points [tbase, tbase + tcnt), or the self pair alone): normal = the normalised
-    // sum of the points' normals, the tangent basis of it, the points' centroid, the torsion radius
-    // (mean tangential distance of the points from the centroid); its normal rows n0 .. n0 + cnt - 1
-    // as a lane mask, its bound weight muw (mu, or mu r for the torsional row), its 16-bit key
-    const bool act = lane < nr;
-    const int rs_ = act ? L.rslot[lane] : 0;
-    const int kind = act ? L.rkind[lane] : 0;
-    const int rbb = L.cbb[rs_];
-    const int rb0 = rbb & 0xFF, rb1 = (rbb >> 8) - 2;
+    return nr;
+}
+
+// The lane's solver row (lane = row), from row_setup to the end of the substep
+struct RowDesc {
+    bool act;      // lane < nr
+    int rs_;       // its slot
+    int kind;      // 0 normal / limit, 1 2 tangential, 3 torsional
+    int rb0, rb1;  // its bodies (rb1: -1 terrain, -2 a joint limit)
+    int rkey;      // its 16-bit key
+    f3 dd, rho;    // the row's linear direction, and its moment about o (a torsional row: the normal)
+    float lam0;    // the previous solve's impulse of the row's key
+};
+// Each row's Jacobian data: slot, kind, bodies; a friction row's patch (a body's terrain points
+// [tbase, tbase + tcnt), or the self pair alone) gives its tangent basis, centroid and torsion
+// radius. The warm start: the previous solve's impulse of each row's key (lane r matches its key
+// against the old keys by readlane and fetches the impulse from lam_prev). Writes wckey (this solve's
+// keys), lam (the friction bound weight muw: mu, or mu r for the torsional row, parked in the impulse
+// words until the solve's set-up: a short live range through the rows' register peak) and row_dirs
+// (the row's linear direction for the reported forces; a joint limit's and a torsional row's: none).
+// No sync at its end: the next phases read these words in the writing lane only.
+HE_DEV void row_setup(Lds& L, int lane, int nr, float mu, float lam_prev, RowDesc& r) {
+    r.act = lane < nr;
+    r.rs_ = r.act ? L.rslot[lane] : 0;
+    r.kind = r.act ? L.rkind[lane] : 0;
+    const int rbb = L.cbb[r.rs_];
+    r.rb0 = rbb & 0xFF;
+    r.rb1 = (rbb >> 8) - 2;
     // the row's 16-bit key: a normal row its slot's, a friction row its patch's (terrain: the body's
     // patch, HE_KEY_PATCH) with the kind
-    const int rkey = kind == 0 ? L.ckey[rs_]
-                               : ((rb1 == -1 ? row_key(rb0, -1, HE_KEY_PATCH, 0) : L.ckey[rs_]) | (kind << 14));
-    // ---- warm start: the previous solve's impulse of each row's key (lane r matches its key against
-    // the old keys by readlane and fetches the impulse)
-    float lam0 = 0.f;
+    r.rkey = r.kind == 0 ? L.ckey[r.rs_]
+                         : ((r.rb1 == -1 ? row_key(r.rb0, -1, HE_KEY_PATCH, 0) : L.ckey[r.rs_]) | (r.kind << 14));
+    r.lam0 = 0.f;
     {
         const int nw = __builtin_amdgcn_readfirstlane(L.nwc);
         if (nw > 0 && nr > 0) {
             const int wk = lane < nw ? L.wckey[lane] : -1;
-            const int ck = act ? rkey : -2;
-            if (nw == nr && __ballot(act && wk != ck) == 0ull) {
-                lam0 = act ? lam_prev : 0.f;  // the same rows in the same order (at rest)
+            const int ck = r.act ? r.rkey : -2;
+            if (nw == nr && __ballot(r.act && wk != ck) == 0ull) {
+                r.lam0 = r.act ? lam_prev : 0.f;  // the same rows in the same order (at rest)
             } else {
                 int src = -1;
                 for (int j = 0; j < nw; ++j) {
@@ -2155,541 +2048,746 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
                     src = (src < 0 && kj == ck) ? j : src;
                 }
                 const float v = __shfl(lam_prev, src >= 0 ? src : 0, W);
-                lam0 = (act && src >= 0) ? v : 0.f;
+                r.lam0 = (r.act && src >= 0) ? v : 0.f;
             }
         }
         // the old keys are matched: this solve's row keys replace them (the next solve's warm start)
-        L.wckey[lane] = act ? rkey : -1;
+        L.wckey[lane] = r.act ? r.rkey : -1;
     }
-    f3 dd, rho;
-    {
-        const f3 xs = f3{L.cx[rs_][0], L.cx[rs_][1], L.cx[rs_][2]};
-        const f3 ns = f3{L.cn[rs_][0], L.cn[rs_][1], L.cn[rs_][2]};
-        // a friction row's patch: the body's terrain patch (above), or a self pair's own point
-        const bool terr = rb1 == -1;
-        const float* pf = L.F[rb0];
-        const f3 np = terr ? f3{pf[0], pf[1], pf[2]} : ns;
-        const f3 xp = terr ? f3{pf[3], pf[4], pf[5]} : xs;
-        const float rp = terr ? prad[rb0] : 0.f;
-        f3 t1, t2;
-        friction_basis(np, t1, t2);
-        dd = kind == 0 ? ns : (kind == 1 ? t1 : (kind == 2 ? t2 : f3{0.f, 0.f, 0.f}));
-        rho = kind == 3 ? np : cross3(kind == 0 ? xs : xp, dd);  // contact points about o
-        // the friction bound weight, parked in the impulse words (dead from the self-pair list to
-        // the solve's store) until the PGS: a short live range through the rows' register peak
-        L.lam[lane] = act && kind > 0 ? (kind == 3 ? mu * rp : mu) : 0.f;
-        // the row's linear direction for the reported forces (IS scratch, read after the solve; a
-        // joint limit's and a torsional row's: none)
-        if (act) {
-            float* fr = gl + 2 * kCand;
-            const bool none = rb1 == -2;
-            fr[3 * lane] = none ? 0.f : dd.x;
-            fr[3 * lane + 1] = none ? 0.f : dd.y;
-            fr[3 * lane + 2] = none ? 0.f : dd.z;
+    const f3 xs = f3{L.cx[r.rs_][0], L.cx[r.rs_][1], L.cx[r.rs_][2]};
+    const f3 ns = f3{L.cn[r.rs_][0], L.cn[r.rs_][1], L.cn[r.rs_][2]};
+    // a friction row's patch: the body's terrain patch (build_rows), or a self pair's own point
+    const bool terr = r.rb1 == -1;
+    const float* pf = L.F[r.rb0];
+    const f3 np = terr ? f3{pf[0], pf[1], pf[2]} : ns;
+    const f3 xp = terr ? f3{pf[3], pf[4], pf[5]} : xs;
+    const float rp = terr ? patch_radius(L)[r.rb0] : 0.f;
+    f3 t1, t2;
+    friction_basis(np, t1, t2);
+    r.dd = r.kind == 0 ? ns : (r.kind == 1 ? t1 : (r.kind == 2 ? t2 : f3{0.f, 0.f, 0.f}));
+    r.rho = r.kind == 3 ? np : cross3(r.kind == 0 ? xs : xp, r.dd);  // contact points about o
+    L.lam[lane] = r.act && r.kind > 0 ? (r.kind == 3 ? mu * rp : mu) : 0.f;
+    if (r.act) {
+        float* fr = row_dirs(L);
+        const bool none = r.rb1 == -2;
+        fr[3 * lane] = none ? 0.f : r.dd.x;
+        fr[3 * lane + 1] = none ? 0.f : r.dd.y;
+        fr[3 * lane + 2] = none ? 0.f : r.dd.z;
+    }
+}
+
+// The rows' system, in registers from row_system to the solve: lane r holds row r of Zh = D^-1/2
+// L^-T J^T (kept for du = L^-1 D^-1/2 Zh^T lambda), lane c column c of the Delassus operator
+struct RowSystem {
+    regla::ZVec z;
+    float acol[MAXR];  // lane c: A[r][c]
+    float brow;        // J_r uf + bias
+    float diag;        // |zh_r|^2 = A[r][r]
+    bool legs;         // every row's support inside the root and the legs (wave-uniform)
+};
+// Contact rows, one per lane (oracle row_jacobian, contact_bias): z = J_r^T, brow = J_r uf + bias,
+// then z <- D^-1/2 L^-T z (dofs outside every row's support stay zero and are skipped
+// wave-uniformly), so that the Delassus operator A = Zh Zh^T is a plain Gram matrix of the lanes'
+// registers. Reads S, u0, yh, sDinv, Lp and the slots; writes no LDS.
+HE_DEV void row_system(Lds& L, const BodyTopo& T, const he_sim_params& p, bool full_dofs, int lane, int nr, float hs,
+                       const RowDesc& r, RowSystem& s, Stamps& st) {
+    using namespace regla;
+    const float dt = p.dt;
+    const uint32_t anc0 = r.act ? T.anc_mask[r.rb0] : 0u;
+    const uint32_t anc1 = (r.act && r.rb1 >= 0) ? T.anc_mask[r.rb1] : 0u;
+    // bodies on some row's support (wave-uniform): the only ones whose dofs can be nonzero
+    const uint32_t lb = wave_or(anc0 | anc1);
+    s.legs = (lb & ~kLegBodies) == 0u && !full_dofs;
+    // z = J_r^T and brow = J_r u0 on the matrix cores
+    zrows_mfma(s.z, lb, anc0, anc1, r.rho, r.dd, L, lane, nr <= 32);
+    // joint-limit rows: the stored row over the joint's three dofs (its support is the joint's
+    // ancestor chain, anc0)
+    const bool limrow = r.act && r.rb1 == -2;
+    if (__ballot(limrow)) {  // wave-uniform
+        const int bl = limrow ? r.rb0 : 0;
+        const float g3[3] = {L.cx[r.rs_][0], L.cx[r.rs_][1], L.cx[r.rs_][2]};
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            const float v = i < 6 ? 0.f : (bl == (i < 6 ? 0 : (i - 6) / 3 + 1) ? g3[i < 6 ? 0 : (i - 6) % 3] : 0.f);
+            ZV(s.z, i) = limrow ? v : ZV(s.z, i);
         }
     }
-    static_assert(2 * kCand + 3 * W <= NG * 6, "per-row force directions fit IS");
-    const float damp = 1.0f / (1.0f + dt * p.angular_damping);
-    float tf1 = 0.f, tf2 = 0.f;  // TGS: the iterations' drive torques, summed per dof (lane, 64 + lane)
-    // TGS: what follows a position iteration's velocity update: its drive torques, the positions by hs
-    // (the last iteration: the step's output velocity), then (not the last) the next iteration's bias
-    // and free motion
-    auto tgs_advance = [&](int it) {
-        const bool lastit = it + 1 == K;
-        tgs_drive_acc(L, lane, tf1, tf2);
-        integrate_bodies(L, T, lane, p, hs, damp, L.u0, lastit, lastit && !last);
-        __builtin_amdgcn_sched_barrier(0);
-        STAMP(12);
-        if (!lastit) {
-            // the velocity-dependent bias: re-evaluated at the start of every second iteration (oracle
-            // g_bias_every: as stable as every iteration at half the passes), else the one in L.uf
-            if (p.bias_midpoint && ((it + 1) % kTgsBiasEvery) == 0) {
-                float b1, b2;
-                tgs_bias_at(L, T, lane, p, L.u0, b1, b2);
-                L.uf[lane] = b1;
-                if (lane < NH) L.uf[64 + lane] = b2;
-            }
-            const float c1 = L.uf[lane];
-            const float c2 = lane < NH ? L.uf[64 + lane] : 0.f;
-            __builtin_amdgcn_sched_barrier(0);
-            STAMP(29);
-            tgs_rhs(L, T, lane, hs, c1, c2);
-            __builtin_amdgcn_sched_barrier(0);
-            STAMP(30);
-        }
-    };
-    // TGS: the reported drive force, the iterations' mean (the joint-limit force is added by the caller)
-    auto tgs_drive_out = [&]() {
-        if (lane >= 6) L.dforce[lane >= 6 ? lane - 6 : 0] = tf1 / (float)K;
-        if (lane < NH) L.dforce[58 + lane] = tf2 / (float)K;
-        sync();
-    };
-    if (nr > 0) {
-        // ---- contact rows, one per lane: z = J_r^T, brow = J_r uf + bias, then z <- D^-1/2 L^-T z
-        // (dofs outside every row's support stay zero and are skipped wave-uniformly), so that the
-        // Delassus operator A = Zh Zh^T is a plain Gram matrix of the lanes' registers
-        float brow = 0.f, diag = 0.f, lamv = 0.f;
-        float acol[MAXR];  // lane c: A[r][c]
-        regla::ZVec z;     // lane r: row r of Zh = D^-1/2 L^-T J^T, kept for du = L^-1 D^-1/2 Zh^T lambda
-        bool legs;         // every row's support inside the root and the legs (wave-uniform)
-        {
-            const uint32_t anc0 = act ? T.anc_mask[rb0] : 0u;
-            const uint32_t anc1 = (act && rb1 >= 0) ? T.anc_mask[rb1] : 0u;
-            // bodies on some row's support (wave-uniform): the only ones whose dofs can be nonzero
-            const uint32_t lb = wave_or(anc0 | anc1);
-            legs = (lb & ~kLegBodies) == 0u && !a.full_dofs;
-            // z = J_r^T and brow = J_r u0 on the matrix cores
-            zrows_mfma(z, lb, anc0, anc1, rho, dd, L, lane, nr <= 32);
-            // joint-limit rows: the stored row over the joint's three dofs (its support is the joint's
-            // ancestor chain, anc0)
-            const bool limrow = act && rb1 == -2;
-            if (__ballot(limrow)) {  // wave-uniform
-                const int bl = limrow ? rb0 : 0;
-                const float g3[3] = {L.cx[rs_][0], L.cx[rs_][1], L.cx[rs_][2]};
+    // J_r u0 on the register pairs (dof i into sum i mod 4); over the legs' dofs only when every
+    // row's support is there (the dropped terms are fma(0, u, s) = s: the same bits)
+    s.brow = s.legs ? zdot_lds<KZ>(s.z, L.u0) : zdot_lds<NG>(s.z, L.u0);
+    if (r.act && r.kind == 0) {
+        const float g = L.cgap[r.rs_];
+        // speculative: close within the solve's step; penetrating: recover at baumgarte per physics
+        // step (TGS too: oracle contact_bias)
+        s.brow += g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
+    }
+    STAMP(PH_ROWS_JT);
+    __builtin_amdgcn_s_setprio(kPrioSerial);
+    zbs<NG - 1>(L.Lp, s.z, lb);
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    STAMP(PH_ROWS_LT);
+    // z <- D^-1/2 z: the scale of dof i is broadcast from lane i's register (no LDS)
+    const float sdl = L.sDinv[lane], sdl2 = lane < NH ? L.sDinv[64 + lane] : 0.f;
+    // then |zh_r|^2 and J_r (uf - u0) = zh_r . yh, yh_i broadcast from lane i (v_readlane: no LDS
+    // loads to hoist into registers at the phase's register peak), four lanes per block into
+    // four SGPRs (one hazard nop per block; through one SGPR the 75 products serialised: this
+    // phase -10 %, the launch -0.5 % by A/B, bit-identical, round 4). Leg support: dofs 0..KZ-1
+    // (zh is exactly zero past them: the same bits)
+    const float yhl = L.yh[lane];
+    if (s.legs) {
+        scale_rows<0, KZ>(s.z, sdl, sdl2);
+        s.diag = znorm2<KZ>(s.z);
+        s.brow += zdot_lanes<KZ>(s.z, yhl, 0.f);
+    } else {
+        scale_rows<0>(s.z, sdl, sdl2);
+        s.diag = znorm2<NG>(s.z);
+        s.brow += zdot_lanes(s.z, yhl, lane < NH ? L.yh[64 + lane] : 0.f);
+    }
+    // dof groups of four touching a support body (wave-uniform, from lb)
+    uint32_t live = 0u;
 #pragma unroll
-                for (int i = 0; i < NG; ++i) {
-                    const float v = i < 6 ? 0.f : (bl == (i < 6 ? 0 : (i - 6) / 3 + 1) ? g3[i < 6 ? 0 : (i - 6) % 3] : 0.f);
-                    ZV(z, i) = limrow ? v : ZV(z, i);
-                }
-            }
-            // J_r u0 on the register pairs (dof i into sum i mod 4); over the legs' dofs only when every
-            // row's support is there (the dropped terms are fma(0, u, s) = s: the same bits)
-            brow = (HE_TGS_LEGS_ROWS && legs) ? zdot_lds<KZ>(z, L.u0) : zdot_lds<NG>(z, L.u0);
-            if (act && kind == 0) {
-                const float g = L.cgap[rs_];
-                // speculative: close within the solve's step; penetrating: recover at baumgarte per physics
-                // step (TGS too: oracle contact_bias)
-                brow += g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
-            }
-            STAMP(20);
-            __builtin_amdgcn_s_setprio(kPrioSerial);
-            zbs<NG - 1>(L.Lp, z, lb);
-            __builtin_amdgcn_s_setprio(kPrioDefault);
-            STAMP(21);
-            // z <- D^-1/2 z: the scale of dof i is broadcast from lane i's register (no LDS)
-            const float sdl = L.sDinv[lane], sdl2 = lane < NH ? L.sDinv[64 + lane] : 0.f;
-            // then |zh_r|^2 and J_r (uf - u0) = zh_r . yh, yh_i broadcast from lane i (v_readlane: no LDS
-            // loads to hoist into registers at the phase's register peak), four lanes per block into
-            // four SGPRs (one hazard nop per block; through one SGPR the 75 products serialised: this
-            // phase -10 %, the launch -0.5 % by A/B, bit-identical, round 4). Leg support: dofs 0..KZ-1
-            // (zh is exactly zero past them: the same bits)
-            const float yhl = L.yh[lane];
-            if (HE_TGS_LEGS_ROWS && legs) {
-                scale_rows<0, KZ>(z, sdl, sdl2);
-                diag = znorm2<KZ>(z);
-                brow += zdot_lanes_legs(z, yhl);
-            } else {
-                scale_rows<0>(z, sdl, sdl2);
-                diag = znorm2<NG>(z);
-                brow += zdot_lanes(z, yhl, lane < NH ? L.yh[64 + lane] : 0.f);
-            }
-            // dof groups of four touching a support body (wave-uniform, from lb)
-            uint32_t live = 0u;
+    for (int g = 0; g < NGRP; ++g)
+        if (lb & kGroupBodies[g]) live |= 1u << g;
+    STAMP(PH_ZROWS);
+    // Delassus columns on the matrix cores: A[r][c] = sum_i zh_r[i] zh_c[i]
+    if (nr <= 32) delassus_mfma<false>(s.z, s.acol, live);  // wave-uniform
+    else if (nr <= 48) delassus_mfma48(s.z, s.acol, live);
+    else delassus_mfma<true>(s.z, s.acol, live);
+}
+
+// ---------------------------------------------------------------------------------- the solves
+// What the PGS and the TGS solve share. Each helper takes the values its caller has (TGS passes a
+// readfirstlane'd row count, PGS the plain one); it chooses none.
+
+// A x over the first NRW rows (lane c of acol holds A[r][c] = A[c][r]; x_r broadcast from lane r):
+// four independent accumulation chains, broadcasts in blocks of 4
+template <int NRW>
+HE_DEV float ax_rows(const float (&acol)[MAXR], float x) {
+    float wa[4] = {0.f, 0.f, 0.f, 0.f};
+    regla::static_for<0, NRW, 4>([&](auto rc) {
+        constexpr int r0 = decltype(rc)::value;
+        float sv[4];
+        regla::rdlane4<r0>(x, sv);
 #pragma unroll
-            for (int g = 0; g < NGRP; ++g)
-                if (lb & kGroupBodies[g]) live |= 1u << g;
-            STAMP(8);
-            // ---- Delassus columns on the matrix cores: A[r][c] = sum_i zh_r[i] zh_c[i]
-            if (nr <= 32) delassus_mfma32(z, acol, live);  // wave-uniform
-            else if (nr <= 48) delassus_mfma48(z, acol, live);
-            else delassus_mfma(z, acol, live);
-        }
-        STAMP(9);
-        if constexpr (TGS) {
-            // ---- TGS position iterations (oracle substep_tgs): each one Gauss-Seidel sweep on the
-            // accumulated impulses, started from them plus the previous iteration's change (the first:
-            // the cached change of the previous step), against J u of the iteration's free velocity and
-            // the bias of the row's separation, advanced by hs J_r u after each iteration
-            const float invd = 1.0f / (act ? diag + 1e-12f : 1.f);
-            const float ninvd = -invd;
-            const int nrb = __builtin_amdgcn_readfirstlane(nr);
-            // the first iteration starts from the cached (previous step's) impulses' per-iteration share g0;
-            // its residual w = brow + A g0 (lane c of acol holds A[r][c] = A[c][r])
-            const float g0 = lam0 * (1.0f / (float)K);
-            float w0 = brow;
-            if (__ballot(g0 != 0.f)) {  // wave-uniform; rows >= nr hold no impulse
-                auto aw = [&](auto nrows) {
-                    constexpr int NRW = decltype(nrows)::value;
-                    float wa[4] = {0.f, 0.f, 0.f, 0.f};
-                    regla::static_for<0, NRW, 4>([&](auto rc) {
-                        constexpr int r0 = decltype(rc)::value;
-                        float sv[4];
-                        regla::rdlane4<r0>(g0, sv);
+        for (int q = 0; q < 4; ++q)
+            if (r0 + q < NRW) wa[(r0 + q) & 3] = fmaf(acol[r0 + q < NRW ? r0 + q : 0], sv[q], wa[(r0 + q) & 3]);
+    });
+    return (wa[0] + wa[1]) + (wa[2] + wa[3]);
+}
+// the warm start's residual share A x by row-count class (wave-uniform; rows >= nrows hold no impulse)
+HE_DEV float warm_residual(const float (&acol)[MAXR], float x, int nrows) {
+    if (nrows <= 16) return ax_rows<16>(acol, x);
+    else if (nrows <= 32) return ax_rows<32>(acol, x);
+    else if (nrows <= 48) return ax_rows<48>(acol, x);
+    else return ax_rows<MAXR>(acol, x);
+}
+
+// a friction row's patch: its normal rows n0 .. n0 + pc - 1 as a 64-bit lane mask (other rows: 0)
+struct PatchMask { uint32_t mlo, mhi; int n0; };
+HE_DEV PatchMask patch_mask(const Lds& L, const RowDesc& r, int lane) {
+    PatchMask m{0u, 0u, 0};
+    const bool isn = r.kind == 0;
+    if (r.act && !isn) {
+        const int pc = r.rb1 == -1 ? L.tcnt[r.rb0] : 1;
+        const uint64_t pm = ((1ull << pc) - 1ull) << (lane - (r.kind - 1) - pc);
+        m.mlo = (uint32_t)pm;
+        m.mhi = (uint32_t)(pm >> 32);
+    }
+    m.n0 = r.act && !isn ? (int)__builtin_ctzll(((uint64_t)m.mhi << 32) | m.mlo) : 0;
+    return m;
+}
+// a friction row's bound: muw x the patch's normal impulses lv (<= 4 rows)
+HE_DEV float patch_bound(float lv, const PatchMask& m, float muw) {
+    float bnd = 0.f;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (r0 + q < NRW) wa[(r0 + q) & 3] = fmaf(acol[r0 + q < NRW ? r0 + q : 0], sv[q], wa[(r0 + q) & 3]);
-                    });
-                    w0 += (wa[0] + wa[1]) + (wa[2] + wa[3]);
-                };
-                if (nrb <= 16) aw(std::integral_constant<int, 16>{});
-                else if (nrb <= 32) aw(std::integral_constant<int, 32>{});
-                else if (nrb <= 48) aw(std::integral_constant<int, 48>{});
-                else aw(std::integral_constant<int, MAXR>{});
-            }
-            float dl = 0.f;
-            // the iterations, for one row-count class of columns held in registers (<= 32 rows: a
-            // standing body's 28; more: the 63-row form), so that the common case keeps 31 registers free
-            // for the phases between the sweeps
-            auto tgs_solve = [&](auto ncls) {
-            constexpr int NC = decltype(ncls)::value;
-            // the iterations' Zh products over dofs 0..KZ-1 when every row's support is in the legs: a
-            // wave-uniform branch inside the one instantiation (its own instantiation, with Zh's other 44
-            // registers dead, ran the standing body as fast but every other env 1-2 % slower: the
-            // second copy of the loop body; profiles/r06/ab_tgs_legs.txt)
-            const bool legs_it = HE_TGS_LEGS && NC == 32 && legs;
-            // the sweep's columns -A[r][lane] / A[lane][lane] of the class's rows; up to 32 rows packed
-            // with their bound weights as the PGS sweep's (pgs_sweep_fix), past 32 the weights rebuilt
-            // per row (pgs_sweep_tgs: 63 registers fewer)
-            constexpr bool PACK = NC <= 32;
-            float ap[PACK ? 1 : NC];
-            regla::f2v ak[PACK ? NC : 1];
-            const bool isn = kind == 0;
-            const float muw = L.lam[lane];  // the friction bound weight parked by the row set-up
-            uint32_t mlo = 0u, mhi = 0u;
-            if (act && !isn) {
-                const int pc = rb1 == -1 ? L.tcnt[rb0] : 1;
-                const uint64_t pm = ((1ull << pc) - 1ull) << (lane - (kind - 1) - pc);
-                mlo = (uint32_t)pm;
-                mhi = (uint32_t)(pm >> 32);
-            }
-            const int n0 = act && !isn ? (int)__builtin_ctzll(((uint64_t)mhi << 32) | mlo) : 0;
-            {
-                auto prep = [&](auto r0c) {
-                    constexpr int R0 = decltype(r0c)::value;
+    for (int j = 0; j < 4; ++j) {
+        const float v = __shfl(lv, (m.n0 + j) & (W - 1), W);
+        const int bit = m.n0 + j;
+        const bool in = bit < 32 ? ((m.mlo >> (bit & 31)) & 1u) : ((m.mhi >> (bit & 31)) & 1u);
+        bnd += in ? v : 0.f;
+    }
+    return bnd * muw;
+}
+
+// The sweep's columns -A[r][lane] / A[lane][lane] of a row-count class of NC rows. PACK: each with
+// its row's bound weight as a register pair (pgs_sweep_fix); else the columns alone, the weights
+// rebuilt per row (pgs_sweep_tgs: NC registers fewer).
+template <int NC, bool PACK>
+struct Columns {
+    float ap[PACK ? 1 : NC];
+    regla::f2v ak[PACK ? NC : 1];
+};
+template <int R0, int NC, bool PACK>
+HE_DEV void prep_block(Columns<NC, PACK>& c, const float (&acol)[MAXR], float ninvd, const PatchMask& m, float muw) {
 #pragma unroll
-                    for (int r = R0; r < (R0 + 16 < NC ? R0 + 16 : NC); ++r) {
-                        if constexpr (PACK) {
-                            const int sel = __builtin_amdgcn_sbfe((int)(r < 32 ? mlo : mhi), r & 31, 1);
-                            ak[r] = regla::f2v{acol[r] * ninvd, __int_as_float(sel & __float_as_int(muw))};
-                        } else {
-                            ap[r] = acol[r] * ninvd;
-                        }
-                    }
-                };
-                prep(std::integral_constant<int, 0>{});
-                if (nrb > 16) prep(std::integral_constant<int, 16>{});
-                if constexpr (NC > 32) {
-                    if (nrb > 32) prep(std::integral_constant<int, 32>{});
-                    if (nrb > 48) prep(std::integral_constant<int, 48>{});
-                }
-            }
-            auto patch_bound = [&](float lv) {  // muw x the patch's normal impulses (<= 4 rows)
-                float bnd = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = __shfl(lv, (n0 + j) & (W - 1), W);
-                    const int bit = n0 + j;
-                    const bool in = bit < 32 ? ((mlo >> (bit & 31)) & 1u) : ((mhi >> (bit & 31)) & 1u);
-                    bnd += in ? v : 0.f;
-                }
-                return bnd * muw;
-            };
-            auto gbias = [&](float g) {
-                return g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
-            };
-            const float kInf = __builtin_inff();
-            float sep = act && isn ? L.cgap[rs_] : 0.f;  // the row's separation (a limit row: its angle gap)
-            float bb = act && isn ? gbias(sep) : 0.f;   // its bias (brow holds it)
-            float applied = 0.f;                         // the impulse already in the working velocity
-            lamv = g0;
-            float cd = act ? -w0 * invd : 0.f;
-            float bnd = patch_bound(lamv);
-            float lo = isn ? -lamv : -bnd - lamv;
-            float hi = isn ? kInf : bnd - lamv;
-            const int nru = __builtin_amdgcn_readfirstlane(nr);
-            for (int it = 0; it < K; ++it) {
-                float dvec = 0.f;
-                int nrs = nru;
-                asm volatile("" : "+s"(nrs));
-                regla::f2v ch = {cd, hi};
-                __builtin_amdgcn_s_setprio(kPrioSerial);
-                if constexpr (PACK) {
-                    if (nrs <= 16) pgs_sweep_fix<0, 16, NC>(ch, dvec, lo, ak, nrs);
-                    else pgs_sweep_fix<0, 32, NC>(ch, dvec, lo, ak, nrs);
-                } else {
-                    if (nrs <= 48) pgs_sweep_tgs<0, 48, NC>(ch, dvec, lo, ap, mlo, mhi, muw, nrs);
-                    else pgs_sweep_tgs<0, MAXR, NC>(ch, dvec, lo, ap, mlo, mhi, muw, nrs);
-                }
-                __builtin_amdgcn_s_setprio(kPrioDefault);
-                STAMP(10);
-                cd = ch.x;
-                lamv += dvec;
-                dl = act ? lamv - applied : 0.f;  // this iteration's impulse change
-                applied = lamv;
-                const float v = act ? -cd * (diag + 1e-12f) - bb : 0.f;  // J_r u after the sweep
-                float e1, e2;  // Zh^T dl, lane = dof (and 64 + lane): also the next start's A dl = Zh (Zh^T dl)
-                __builtin_amdgcn_sched_barrier(0);  // phase fences: each phase's temporaries beside the
-                if (legs_it) {                          // loop's long-lived rows and columns, not several
-                    e1 = reduce_scatter_z_legs(z, dl);
-                    e2 = 0.f;
-                } else {
-                    reduce_scatter_z(z, dl, lane, e1, e2);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                e2 = lane < NH ? e2 : 0.f;
-                tgs_velocity(L, T, lane, e1, e2);  // the working velocity: u += L^-1 D^-1/2 (yh + Zh^T dl)
-                __builtin_amdgcn_sched_barrier(0);
-                STAMP(11);
-                if (isn) sep += hs * v;
-                const bool lastit = it + 1 == K;
-                tgs_advance(it);
-                __builtin_amdgcn_sched_barrier(0);
-                if (!lastit) {
-                    // the next sweep's start about lambda = applied + dl: w = J u + zh . yh + bias(sep) + A dl,
-                    // with zh . yh + A dl = zh . (yh + Zh^T dl), one dot product
-                    const float yhl = L.yh[lane] + e1;
-                    float zy;
-                    if (legs_it) {
-                        zy = zdot_lanes_legs(z, yhl);
-                    } else {
-                        const float yh2 = lane < NH ? L.yh[64 + lane] + e2 : 0.f;
-                        zy = zdot_lanes(z, yhl, yh2);
-                    }
-                    bb = act && isn ? gbias(sep) : 0.f;
-                    lamv = applied + dl;
-                    cd = act ? -(v + zy + bb) * invd : 0.f;
-                    bnd = patch_bound(lamv);
-                    lo = isn ? -lamv : -bnd - lamv;
-                    hi = isn ? kInf : bnd - lamv;
-                    STAMP(31);
-                }
-            }
-            };
-            if (nrb <= 32) tgs_solve(std::integral_constant<int, 32>{});
-#ifdef HE_TGS_CLASS32_ONLY  // diagnostic A/B only (wrong past 32 rows): what the 63-row class costs the common path
-            else tgs_solve(std::integral_constant<int, 32>{});
-#else
-            else tgs_solve(std::integral_constant<int, MAXR>{});
-#endif
-            // the cache and the reported forces take the step's accumulated impulses
-            L.lam[lane] = act ? lamv : 0.f;
-            if (lane == 0) L.nwc = p.warm_start ? nr : 0;
-            tgs_drive_out();
-            // the joint-limit force (dof_force = drive and limit together): limit row c = slot c
-            const int nl = __builtin_amdgcn_readfirstlane(L.nlim);
-            if (lane < nl) {
-                const int d0 = 3 * ((L.cbb[lane < MAXC ? lane : 0] & 0xFF) - 1);
-                const float lf = lamv / dt;
-                L.dforce[d0] += L.cx[lane < MAXC ? lane : 0][0] * lf;
-                L.dforce[d0 + 1] += L.cx[lane < MAXC ? lane : 0][1] * lf;
-                L.dforce[d0 + 2] += L.cx[lane < MAXC ? lane : 0][2] * lf;
-            }
-            sync();
+    for (int r = R0; r < (R0 + 16 < NC ? R0 + 16 : NC); ++r) {
+        if constexpr (PACK) {
+            const int sel = __builtin_amdgcn_sbfe((int)(r < 32 ? m.mlo : m.mhi), r & 31, 1);
+            c.ak[r] = regla::f2v{acol[r] * ninvd, __int_as_float(sel & __float_as_int(muw))};
         } else {
-        // ---- projected Gauss-Seidel over the rows (pgs_sweep): lane r keeps its unconstrained change,
-        // its impulse and its bounds
-        {
-            const float invd = 1.0f / (act ? diag + 1e-12f : 1.f);
-            // residual at the warm start: w = brow + A lambda0 (acol: lane c holds A[r][c] = A[c][r])
-            float w0 = brow;
-            if (__ballot(lam0 != 0.f)) {  // wave-uniform; rows >= nr hold no impulse
-                auto aw = [&](auto nrows) {  // four independent accumulation chains, broadcasts in blocks of 4
-                    constexpr int NRW = decltype(nrows)::value;
-                    float wa[4] = {0.f, 0.f, 0.f, 0.f};
-                    regla::static_for<0, NRW, 4>([&](auto rc) {
-                        constexpr int r0 = decltype(rc)::value;
-                        float sv[4];
-                        regla::rdlane4<r0>(lam0, sv);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (r0 + q < NRW) wa[(r0 + q) & 3] = fmaf(acol[r0 + q], sv[q], wa[(r0 + q) & 3]);
-                    });
-                    w0 += (wa[0] + wa[1]) + (wa[2] + wa[3]);
-                };
-                if (nr <= 16) aw(std::integral_constant<int, 16>{});
-                else if (nr <= 32) aw(std::integral_constant<int, 32>{});
-                else if (nr <= 48) aw(std::integral_constant<int, 48>{});
-                else aw(std::integral_constant<int, MAXR>{});
-            }
-            lamv = lam0;
-            float cd = act ? -w0 * invd : 0.f;
-            const float ninvd = -invd;
-            // the row's friction bound weight and its patch's normal rows n0 .. n0 + pc - 1 as a
-            // 64-bit lane mask (friction rows only)
-            const bool isn = kind == 0;
-            const float muw = L.lam[lane];
-            uint32_t mlo = 0u, mhi = 0u;
-            if (act && !isn) {
-                const int pc = rb1 == -1 ? L.tcnt[rb0] : 1;
-                const uint64_t pm = ((1ull << pc) - 1ull) << (lane - (kind - 1) - pc);
-                mlo = (uint32_t)pm;
-                mhi = (uint32_t)(pm >> 32);
-            }
-            // a friction row's bound at the warm start: muw x its patch's normal impulses (<= 4 rows)
-            float bnd = 0.f;
-            if (__ballot(lam0 != 0.f)) {
-                const int n0 = act && !isn ? (int)__builtin_ctzll(((uint64_t)mhi << 32) | mlo) : 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = __shfl(lam0, (n0 + j) & (W - 1), W);
-                    const int bit = n0 + j;
-                    const bool in = bit < 32 ? ((mlo >> (bit & 31)) & 1u) : ((mhi >> (bit & 31)) & 1u);
-                    bnd += in ? v : 0.f;
-                }
-                bnd *= muw;
-            }
-            regla::f2v ak[MAXR];
-            // the scaled columns acolp[r] = -A[r][lane] / A[lane][lane] and the packed bound weights of
-            // the row-count class's rows only (the branch-free sweep reads no row past its class):
-            // blocks of 16 rows, each behind a wave-uniform row-count test
-            {
-                const int nrb = __builtin_amdgcn_readfirstlane(nr);
-                auto prep = [&](auto r0c) {
-                    constexpr int R0 = decltype(r0c)::value;
-#pragma unroll
-                    for (int r = R0; r < (R0 + 16 < MAXR ? R0 + 16 : MAXR); ++r) {
-                        const int sel = __builtin_amdgcn_sbfe((int)(r < 32 ? mlo : mhi), r & 31, 1);
-                        ak[r] = regla::f2v{acol[r] * ninvd, __int_as_float(sel & __float_as_int(muw))};
-                    }
-                };
-                prep(std::integral_constant<int, 0>{});
-                if (nrb > 16) prep(std::integral_constant<int, 16>{});
-                if (nrb > 32) prep(std::integral_constant<int, 32>{});
-                if (nrb > 48) prep(std::integral_constant<int, 48>{});
-            }
-            const float kInf = __builtin_inff();
-            float lo = isn ? -lamv : -bnd - lamv;
-            float hi = isn ? kInf : bnd - lamv;
-            const int nru = __builtin_amdgcn_readfirstlane(nr);
-            STAMP(22);  // the solve's set-up (warm-start residual, bounds, scaled columns) apart from its sweeps
-            __builtin_amdgcn_s_setprio(kPrioSerial);
-            const float tol = p.solver_tolerance;
-            for (int it = 0; it < p.solver_iterations; ++it) {
-                float dvec = 0.f;
-                // the row count through an opaque copy per sweep: the 63 early-exit compares stay
-                // scalar compares in the sweep instead of being hoisted out of the loop as 63
-                // lane-mask pairs (SGPR spills)
-                int nrs = nru;
-                asm volatile("" : "+s"(nrs));
-                regla::f2v ch = {cd, hi};
-                if (nrs <= 16) pgs_sweep_fix<0, 16>(ch, dvec, lo, ak, nrs);
-                else
-                if (nrs <= 32) pgs_sweep_fix<0, 32>(ch, dvec, lo, ak, nrs);
-                else if (nrs <= 48) pgs_sweep_fix<0, 48>(ch, dvec, lo, ak, nrs);
-                else pgs_sweep_fix<0, MAXR>(ch, dvec, lo, ak, nrs);
-                cd = ch.x;
-                hi = ch.y;
-                // the bound at the sweep's end: B = hi + lambda(start); then the bounds about the new impulse
-                const float bn = hi + lamv;
-                lamv += dvec;
-                lo = isn ? -lamv : -bn - lamv;
-                hi = isn ? kInf : bn - lamv;
-                // converged (optional, solver_tolerance > 0): no row's velocity moved by more than
-                // the tolerance in this sweep, |d lambda_r| A_rr (oracle: the same test)
-                if (tol > 0.f && __ballot(act && fabsf(dvec) * diag > tol) == 0ull) break;
-            }
-            __builtin_amdgcn_s_setprio(kPrioDefault);
+            c.ap[r] = acol[r] * ninvd;
         }
-        // the solve's impulses and row keys: the next solve's warm start and the reported forces
-        L.lam[lane] = act ? lamv : 0.f;
-        if (lane == 0) L.nwc = p.warm_start ? nr : 0;  // warm_start 0: every substep's solve is cold
-        sync();
-        STAMP(10);
-        // ---- du = M^-1 J^T lambda = L^-1 D^-1/2 (Zh^T lambda): lane r scales its row by lambda_r,
-        // a wave reduce-scatter sums the 75 columns into lane = dof, then one L^-1 sweep
-        {
-            __builtin_amdgcn_s_setprio(kPrioDefault);
-            float v64[64], v16[16];
-#pragma unroll
-            for (int i = 0; i < 64; ++i) v64[i] = ZV(z, i) * lamv;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v16[i] = 64 + i < NG ? ZV(z, 64 + i < NG ? 64 + i : 0) * lamv : 0.f;
-            float yl = reduce_scatter<64>(v64);
-            float y2 = __shfl(reduce_scatter<16>(v16), 4 * (lane & 15), W);
-            yl = (yl + L.yh[lane]) * L.sDinv[lane];
-            y2 = lane < NH ? (y2 + L.yh[64 + lane]) * L.sDinv[64 + lane] : 0.f;
-            float r1[regla::kRowRegs], r2[regla::kRowRegs];
-            load_rows(L, T, lane, r1, r2);
-            solve_L(r1, r2, lane, yl, y2);
-            __builtin_amdgcn_s_setprio(kPrioDefault);
-            L.uf[lane] = L.u0[lane] + yl;
-            if (lane < NH) L.uf[64 + lane] = L.u0[64 + lane] + y2;
+    }
+}
+// the columns of the row-count class's rows only (the branch-free sweep reads no row past its
+// class): blocks of 16 rows, each behind a wave-uniform row-count test
+template <int NC, bool PACK>
+HE_DEV void prep_columns(Columns<NC, PACK>& c, const float (&acol)[MAXR], float ninvd, const PatchMask& m, float muw,
+                         int nrb) {
+    prep_block<0>(c, acol, ninvd, m, muw);
+    if (nrb > 16) prep_block<16>(c, acol, ninvd, m, muw);
+    if constexpr (NC > 32) {
+        if (nrb > 32) prep_block<32>(c, acol, ninvd, m, muw);
+        if (nrb > 48) prep_block<48>(c, acol, ninvd, m, muw);
+    }
+}
+
+// The joint-limit force added to dof_force (the joint's solver force, drive and limit together;
+// oracle/he_oracle_physics.c): limit slot c (one per joint, row c) adds g lambda / dt over its
+// joint's dofs, g = its row (kept in the contact-position words). lam: the lane's row impulse.
+HE_DEV void add_limit_force(Lds& L, int lane, float lam, float dt) {
+    const int nl = __builtin_amdgcn_readfirstlane(L.nlim);
+    if (lane < nl) {
+        const int d0 = 3 * ((L.cbb[lane < MAXC ? lane : 0] & 0xFF) - 1);
+        const float lf = lam / dt;
+        L.dforce[d0] += L.cx[lane < MAXC ? lane : 0][0] * lf;
+        L.dforce[d0 + 1] += L.cx[lane < MAXC ? lane : 0][1] * lf;
+        L.dforce[d0 + 2] += L.cx[lane < MAXC ? lane : 0][2] * lf;
+    }
+}
+
+// The TGS position iterations' constants and running sums (oracle substep_tgs): K iterations of
+// hs = dt / K on this step's factor and contact set
+struct TgsStep {
+    int K;
+    float hs, damp;
+    bool last;       // the policy step's last substep
+    float tf1, tf2;  // the iterations' drive torques, summed per dof (lane, 64 + lane)
+};
+// What follows a position iteration's velocity update: its drive torques, the positions by hs (the
+// last iteration: the step's output velocity), then (not the last) the next iteration's bias and
+// free motion
+HE_DEV void tgs_advance(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int it, TgsStep& ts, Stamps& st) {
+    const bool lastit = it + 1 == ts.K;
+    tgs_drive_acc(L, lane, ts.tf1, ts.tf2);
+    integrate_bodies(L, T, lane, p, ts.hs, ts.damp, L.u0, lastit, lastit && !ts.last);
+    __builtin_amdgcn_sched_barrier(0);
+    STAMP(PH_INTEGRATE);
+    if (!lastit) {
+        // the velocity-dependent bias: re-evaluated at the start of every second iteration (oracle
+        // g_bias_every: as stable as every iteration at half the passes), else the one in L.uf
+        if (p.bias_midpoint && ((it + 1) % kTgsBiasEvery) == 0) {
+            float b1, b2;
+            tgs_bias_at(L, T, lane, p, L.u0, b1, b2);
+            L.uf[lane] = b1;
+            if (lane < regla::NH) L.uf[64 + lane] = b2;
         }
-        }  // PGS
-        // ---- reported contact forces (net linear contact impulse per body / dt): the output is the
-        // last substep's, so the earlier substeps skip them (their cf rows stay zero, as set above)
-        if (last) {
-            float* fr = gl + 2 * kCand;  // per-row linear impulses: the stored directions x lambda
-            if (act) {
-                fr[3 * lane] *= lamv;
-                fr[3 * lane + 1] *= lamv;
-                fr[3 * lane + 2] *= lamv;
+        const float c1 = L.uf[lane];
+        const float c2 = lane < regla::NH ? L.uf[64 + lane] : 0.f;
+        __builtin_amdgcn_sched_barrier(0);
+        STAMP(PH_TGS_BIAS);
+        tgs_rhs(L, T, lane, ts.hs, c1, c2);
+        __builtin_amdgcn_sched_barrier(0);
+        STAMP(PH_TGS_RHS);
+    }
+}
+// the reported drive force, the iterations' mean (the joint-limit force is added by the caller)
+HE_DEV void tgs_drive_out(Lds& L, int lane, const TgsStep& ts) {
+    if (lane >= 6) L.dforce[lane >= 6 ? lane - 6 : 0] = ts.tf1 / (float)ts.K;
+    if (lane < regla::NH) L.dforce[58 + lane] = ts.tf2 / (float)ts.K;
+    sync();
+}
+
+// The TGS position iterations for one row-count class of columns held in registers (<= 32 rows: a
+// standing body's 28; more: the 63-row form), so that the common case keeps 31 registers free for
+// the phases between the sweeps. Each iteration is one Gauss-Seidel sweep on the accumulated
+// impulses, started from them plus the previous iteration's change (the first: the cached change of
+// the previous step, g0 with residual w0), against J u of the iteration's free velocity and the bias
+// of the row's separation, advanced by hs J_r u after each iteration. nrb: the row count as a
+// scalar, from the caller (a second readfirstlane here: +11 VGPR spills). Reads lam (the bound
+// weights row_setup parked). Returns the step's accumulated impulse of the lane's row.
+//
+// The leg class (legs_it): the iterations' Zh products over dofs 0..KZ-1 when every row's support is
+// in the legs, a wave-uniform branch inside the one instantiation (its own instantiation, with Zh's
+// other 44 registers dead, ran the standing body as fast but every other env 1-2 % slower: the
+// second copy of the loop body; profiles/r06/ab_tgs_legs.txt). reduce_scatter_z_legs sums in another
+// association order than reduce_scatter_z; the two agree to the bit (which
+// test_leg_class_leaves_the_step_unchanged asserts) only because the terms the leg form leaves out
+// are exact zeros. Precondition: NC == 32 (no row sits on lanes 32..63), and every lane >= nr
+// carries dl == 0 (its `act` is false) with a finite z, so that its products are +-0 and not NaN.
+// A change to how the inactive lanes are handled has to keep both.
+template <int NC>
+HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
+                       const RowSystem& s, int nrb, float g0, float w0, TgsStep& ts, Stamps& st) {
+    using regla::NH;
+    const bool act = r.act;
+    const float hs = ts.hs, dt = p.dt;
+    const float invd = 1.0f / (act ? s.diag + 1e-12f : 1.f);
+    const float ninvd = -invd;
+    const bool legs_it = NC == 32 && s.legs;
+    // up to 32 rows packed with their bound weights as the PGS sweep's, past 32 the weights rebuilt
+    // per row (63 registers fewer)
+    constexpr bool PACK = NC <= 32;
+    Columns<NC, PACK> col;
+    const bool isn = r.kind == 0;
+    const float muw = L.lam[lane];  // the friction bound weight parked by the row set-up
+    const PatchMask pm = patch_mask(L, r, lane);
+    prep_columns(col, s.acol, ninvd, pm, muw, nrb);
+    auto gbias = [&](float g) {
+        return g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
+    };
+    const float kInf = __builtin_inff();
+    float sep = act && isn ? L.cgap[r.rs_] : 0.f;  // the row's separation (a limit row: its angle gap)
+    float bb = act && isn ? gbias(sep) : 0.f;     // its bias (brow holds it)
+    float applied = 0.f;                           // the impulse already in the working velocity
+    float lamv = g0;
+    float dl = 0.f;
+    float cd = act ? -w0 * invd : 0.f;
+    float bnd = patch_bound(lamv, pm, muw);
+    float lo = isn ? -lamv : -bnd - lamv;
+    float hi = isn ? kInf : bnd - lamv;
+    const int nru = __builtin_amdgcn_readfirstlane(nr);
+    for (int it = 0; it < ts.K; ++it) {
+        float dvec = 0.f;
+        // the row count through an opaque copy per sweep (see solve_pgs)
+        int nrs = nru;
+        asm volatile("" : "+s"(nrs));
+        regla::f2v ch = {cd, hi};
+        __builtin_amdgcn_s_setprio(kPrioSerial);
+        if constexpr (PACK) {
+            if (nrs <= 16) pgs_sweep_fix<0, 16, NC>(ch, dvec, lo, col.ak, nrs);
+            else pgs_sweep_fix<0, 32, NC>(ch, dvec, lo, col.ak, nrs);
+        } else {
+            if (nrs <= 48) pgs_sweep_tgs<0, 48, NC>(ch, dvec, lo, col.ap, pm.mlo, pm.mhi, muw, nrs);
+            else pgs_sweep_tgs<0, MAXR, NC>(ch, dvec, lo, col.ap, pm.mlo, pm.mhi, muw, nrs);
+        }
+        __builtin_amdgcn_s_setprio(kPrioDefault);
+        STAMP(PH_PGS);
+        cd = ch.x;
+        lamv += dvec;
+        dl = act ? lamv - applied : 0.f;  // this iteration's impulse change
+        applied = lamv;
+        const float v = act ? -cd * (s.diag + 1e-12f) - bb : 0.f;  // J_r u after the sweep
+        float e1, e2;  // Zh^T dl, lane = dof (and 64 + lane): also the next start's A dl = Zh (Zh^T dl)
+        __builtin_amdgcn_sched_barrier(0);  // phase fences: each phase's temporaries beside the
+        if (legs_it) {                          // loop's long-lived rows and columns, not several
+            e1 = reduce_scatter_z_legs(s.z, dl);
+            e2 = 0.f;
+        } else {
+            reduce_scatter_z(s.z, dl, lane, e1, e2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        e2 = lane < NH ? e2 : 0.f;
+        tgs_velocity(L, T, lane, e1, e2);  // the working velocity: u += L^-1 D^-1/2 (yh + Zh^T dl)
+        __builtin_amdgcn_sched_barrier(0);
+        STAMP(PH_DU_SOLVE);
+        if (isn) sep += hs * v;
+        const bool lastit = it + 1 == ts.K;
+        tgs_advance(L, T, p, lane, it, ts, st);
+        __builtin_amdgcn_sched_barrier(0);
+        if (!lastit) {
+            // the next sweep's start about lambda = applied + dl: w = J u + zh . yh + bias(sep) + A dl,
+            // with zh . yh + A dl = zh . (yh + Zh^T dl), one dot product
+            const float yhl = L.yh[lane] + e1;
+            float zy;
+            if (legs_it) {
+                zy = zdot_lanes<KZ>(s.z, yhl, 0.f);
+            } else {
+                const float yh2 = lane < NH ? L.yh[64 + lane] + e2 : 0.f;
+                zy = zdot_lanes(s.z, yhl, yh2);
             }
-            sync();
-            if (lane < NB) {
-                // the body's own terrain rows (its patch: a contiguous row range, in row order), then
-                // the self-pair rows with their sign; the same summation order as over all rows
-                float F3[3] = {0.f, 0.f, 0.f};
-                const int tn = L.tcnt[lane];
-                const int r0 = tn > 0 ? L.srow0[L.tbase[lane]] : 0;
-                const int rn = tn == 0 ? 0 : tn + (tn >= 2 ? 3 : 2);
+            bb = act && isn ? gbias(sep) : 0.f;
+            lamv = applied + dl;
+            cd = act ? -(v + zy + bb) * invd : 0.f;
+            bnd = patch_bound(lamv, pm, muw);
+            lo = isn ? -lamv : -bnd - lamv;
+            hi = isn ? kInf : bnd - lamv;
+            STAMP(PH_TGS_NEXT);
+        }
+    }
+    return lamv;
+}
+// The TGS solve with contact rows: the first iteration starts from the cached (previous step's)
+// impulses' per-iteration share g0, its residual w = brow + A g0; then the iterations by row-count
+// class; the cache and the reported forces take the step's accumulated impulses. Writes lam, nwc,
+// dforce (drive and joint-limit force).
+HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
+                            const RowSystem& s, TgsStep& ts, Stamps& st) {
+    const int nrb = __builtin_amdgcn_readfirstlane(nr);
+    const float g0 = r.lam0 * (1.0f / (float)ts.K);
+    float w0 = s.brow;
+    if (__ballot(g0 != 0.f)) w0 += warm_residual(s.acol, g0, nrb);  // wave-uniform
+    float lamv;
+    if (nrb <= 32) lamv = solve_tgs<32>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
+    else lamv = solve_tgs<MAXR>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
+    L.lam[lane] = r.act ? lamv : 0.f;
+    if (lane == 0) L.nwc = p.warm_start ? nr : 0;
+    tgs_drive_out(L, lane, ts);
+    add_limit_force(L, lane, lamv, p.dt);  // limit row c = slot c
+    sync();
+    return lamv;
+}
+// TGS without contact rows: the iterations' drives and bias only
+HE_DEV void tgs_free_iterations(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, TgsStep& ts, Stamps& st) {
+    for (int it = 0; it < ts.K; ++it) {
+        tgs_velocity(L, T, lane, 0.f, 0.f);
+        STAMP(PH_DU_SOLVE);
+        tgs_advance(L, T, p, lane, it, ts, st);
+    }
+    tgs_drive_out(L, lane, ts);
+}
+
+// Projected Gauss-Seidel over the rows (pgs_sweep_fix): lane r keeps its unconstrained change, its
+// impulse and its bounds. Reads lam (the bound weights row_setup parked), then writes the solve's
+// impulses there with nwc: the next solve's warm start and the reported forces. Returns the lane's
+// row impulse.
+HE_DEV float solve_pgs(Lds& L, const he_sim_params& p, int lane, int nr, const RowDesc& r, const RowSystem& s, Stamps& st) {
+    const bool act = r.act;
+    const float lam0 = r.lam0;
+    const float invd = 1.0f / (act ? s.diag + 1e-12f : 1.f);
+    // residual at the warm start: w = brow + A lambda0
+    float w0 = s.brow;
+    if (__ballot(lam0 != 0.f)) w0 += warm_residual(s.acol, lam0, nr);  // wave-uniform
+    float lamv = lam0;
+    float cd = act ? -w0 * invd : 0.f;
+    const float ninvd = -invd;
+    const bool isn = r.kind == 0;
+    const float muw = L.lam[lane];
+    const PatchMask pm = patch_mask(L, r, lane);
+    // a friction row's bound at the warm start
+    float bnd = 0.f;
+    if (__ballot(lam0 != 0.f)) bnd = patch_bound(lam0, pm, muw);
+    Columns<MAXR, true> col;
+    prep_columns(col, s.acol, ninvd, pm, muw, __builtin_amdgcn_readfirstlane(nr));
+    const float kInf = __builtin_inff();
+    float lo = isn ? -lamv : -bnd - lamv;
+    float hi = isn ? kInf : bnd - lamv;
+    const int nru = __builtin_amdgcn_readfirstlane(nr);
+    STAMP(PH_PGS_SETUP);  // the solve's set-up (warm-start residual, bounds, scaled columns) apart from its sweeps
+    __builtin_amdgcn_s_setprio(kPrioSerial);
+    const float tol = p.solver_tolerance;
+    for (int it = 0; it < p.solver_iterations; ++it) {
+        float dvec = 0.f;
+        // the row count through an opaque copy per sweep: the 63 early-exit compares stay
+        // scalar compares in the sweep instead of being hoisted out of the loop as 63
+        // lane-mask pairs (SGPR spills)
+        int nrs = nru;
+        asm volatile("" : "+s"(nrs));
+        regla::f2v ch = {cd, hi};
+        if (nrs <= 16) pgs_sweep_fix<0, 16>(ch, dvec, lo, col.ak, nrs);
+        else if (nrs <= 32) pgs_sweep_fix<0, 32>(ch, dvec, lo, col.ak, nrs);
+        else if (nrs <= 48) pgs_sweep_fix<0, 48>(ch, dvec, lo, col.ak, nrs);
+        else pgs_sweep_fix<0, MAXR>(ch, dvec, lo, col.ak, nrs);
+        cd = ch.x;
+        hi = ch.y;
+        // the bound at the sweep's end: B = hi + lambda(start); then the bounds about the new impulse
+        const float bn = hi + lamv;
+        lamv += dvec;
+        lo = isn ? -lamv : -bn - lamv;
+        hi = isn ? kInf : bn - lamv;
+        // converged (optional, solver_tolerance > 0): no row's velocity moved by more than
+        // the tolerance in this sweep, |d lambda_r| A_rr (oracle: the same test)
+        if (tol > 0.f && __ballot(act && fabsf(dvec) * s.diag > tol) == 0ull) break;
+    }
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    L.lam[lane] = act ? lamv : 0.f;
+    if (lane == 0) L.nwc = p.warm_start ? nr : 0;  // warm_start 0: every substep's solve is cold
+    sync();
+    STAMP(PH_PGS);
+    return lamv;
+}
+
+// PGS: uf = u0 + L^-1 D^-1/2 (yh + Zh^T lambda). Lane r scales its row by lambda_r, a wave
+// reduce-scatter sums the 75 columns into lane = dof, then one L^-1 sweep. No sync at its end (the
+// next reader follows one).
+HE_DEV void pgs_velocity(Lds& L, const BodyTopo& T, int lane, const regla::ZVec& z, float lamv) {
+    using regla::NH;
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    float v64[64], v16[16];
 #pragma unroll
-                for (int k = 0; k < 7; ++k) {
-                    if (k < rn) {
-                        const int r = r0 + k;
-                        for (int x = 0; x < 3; ++x) F3[x] += fr[3 * r + x];
-                    }
-                }
-                const int nterr = __builtin_amdgcn_readfirstlane(L.nterr);
-                for (int c = nterr; c < nc; ++c) {  // wave-uniform bounds
-                    const int cb = L.cbb[c];
-                    const float sg = ((cb & 0xFF) == lane ? 1.f : 0.f) - ((cb >> 8) - 2 == lane ? 1.f : 0.f);
-                    const int r = L.srow0[c];
-                    for (int k = 0; k < 3; ++k)
-                        for (int x = 0; x < 3; ++x) F3[x] += sg * fr[3 * (r + k) + x];
-                }
-                L.cf[lane][0] = F3[0] / dt; L.cf[lane][1] = F3[1] / dt; L.cf[lane][2] = F3[2] / dt;
+    for (int i = 0; i < 64; ++i) v64[i] = ZV(z, i) * lamv;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v16[i] = 64 + i < NG ? ZV(z, 64 + i < NG ? 64 + i : 0) * lamv : 0.f;
+    float yl = reduce_scatter<64>(v64);
+    float y2 = __shfl(reduce_scatter<16>(v16), 4 * (lane & 15), W);
+    yl = (yl + L.yh[lane]) * L.sDinv[lane];
+    y2 = lane < NH ? (y2 + L.yh[64 + lane]) * L.sDinv[64 + lane] : 0.f;
+    float r1[regla::kRowRegs], r2[regla::kRowRegs];
+    load_rows(L, T, lane, r1, r2);
+    regla::solve_L_rows<0>(r1, r2, yl, y2);
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    L.uf[lane] = L.u0[lane] + yl;
+    if (lane < NH) L.uf[64 + lane] = L.u0[64 + lane] + y2;
+}
+// PGS without contact rows: uf = u0 + L^-1 D^-1/2 yh
+HE_DEV void free_velocity(Lds& L, const BodyTopo& T, int lane) {
+    using regla::NH;
+    float yl = L.yh[lane] * L.sDinv[lane];
+    float y2 = lane < NH ? L.yh[64 + lane] * L.sDinv[64 + lane] : 0.f;
+    float r1[regla::kRowRegs], r2[regla::kRowRegs];
+    load_rows(L, T, lane, r1, r2);
+    regla::solve_L_rows<0>(r1, r2, yl, y2);
+    L.uf[lane] = L.u0[lane] + yl;
+    if (lane < NH) L.uf[64 + lane] = L.u0[64 + lane] + y2;
+    sync();
+}
+// PGS: the drive force actually applied (the reported one is the last substep's), plus the
+// joint-limit force
+HE_DEV void pgs_drive_out(Lds& L, int lane, int nr, float dt) {
+    for (int i = lane; i < NG; i += W)
+        if (i >= 6) L.dforce[i - 6] -= L.coef[i] * (L.uf[i] - L.u0[i]);
+    sync();
+    if (nr > 0) add_limit_force(L, lane, L.lam[lane], dt);
+    sync();
+}
+
+// Reported contact forces (net linear contact impulse per body / dt), lane = body: the output is the
+// last substep's, so the earlier substeps skip them (their cf rows stay zero, as gen_contacts set
+// them). Turns row_dirs into the per-row linear impulses (the stored directions x lambda).
+HE_DEV void contact_forces_out(Lds& L, int lane, int nc, bool act, float lamv, float dt) {
+    float* fr = row_dirs(L);
+    if (act) {
+        fr[3 * lane] *= lamv;
+        fr[3 * lane + 1] *= lamv;
+        fr[3 * lane + 2] *= lamv;
+    }
+    sync();
+    if (lane < NB) {
+        // the body's own terrain rows (its patch: a contiguous row range, in row order), then
+        // the self-pair rows with their sign; the same summation order as over all rows
+        float F3[3] = {0.f, 0.f, 0.f};
+        const int tn = L.tcnt[lane];
+        const int r0 = tn > 0 ? L.srow0[L.tbase[lane]] : 0;
+        const int rn = tn == 0 ? 0 : tn + (tn >= 2 ? 3 : 2);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            if (k < rn) {
+                const int r = r0 + k;
+                for (int x = 0; x < 3; ++x) F3[x] += fr[3 * r + x];
             }
-            sync();
-        }  // last
+        }
+        const int nterr = __builtin_amdgcn_readfirstlane(L.nterr);
+        for (int c = nterr; c < nc; ++c) {  // wave-uniform bounds
+            const int cb = L.cbb[c];
+            const float sg = ((cb & 0xFF) == lane ? 1.f : 0.f) - ((cb >> 8) - 2 == lane ? 1.f : 0.f);
+            const int r = L.srow0[c];
+            for (int k = 0; k < 3; ++k)
+                for (int x = 0; x < 3; ++x) F3[x] += sg * fr[3 * (r + k) + x];
+        }
+        L.cf[lane][0] = F3[0] / dt; L.cf[lane][1] = F3[1] / dt; L.cf[lane][2] = F3[2] / dt;
+    }
+    sync();
+}
+
+// ---------------------------------------------------------------------------------- one substep
+template <bool TGS>
+HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
+                    const float* mass_scale, float mu, int tkind, Stamps& st, bool first, bool last) {
+    // the launch arguments through an opaque offset too: their fields are re-read (scalar loads
+    // from the kernarg segment) where used instead of being held in SGPRs across the substep loop
+    int ao = 0;
+    asm volatile("" : "+s"(ao));
+    const PhysArgs& a = *reinterpret_cast<const PhysArgs*>(reinterpret_cast<const char*>(&a0) + ao);
+    // opaque per substep: keeps the compiler from hoisting ~1k uniform model loads out of the
+    // substep loop into SGPRs (which then spill into VGPR lanes)
+    // (an opaque byte offset rather than an opaque pointer: the pointer keeps its global address
+    // space, so the loads stay global_load / s_load instead of flat_load)
+    int mo = 0;
+    asm volatile("" : "+s"(mo));
+    const he_model& m = *reinterpret_cast<const he_model*>(reinterpret_cast<const char*>(mp) + mo);
+    // likewise an opaque VGPR base for LDS: addresses become base + immediate offset instead of
+    // hundreds of hoisted uniform address constants
+    int lds_off = 0;
+    asm volatile("" : "+v"(lds_off));
+    Lds& L = *reinterpret_cast<Lds*>(reinterpret_cast<char*>(&L0) + lds_off);
+    // and the lane id: the many per-lane predicates of the unrolled algebra are then rebuilt
+    // next to their use instead of being hoisted as loop invariants
+    asm volatile("" : "+v"(lane));
+    const BodyTopo& T = L.T;
+    const he_sim_params& p = a.p;
+    const float dt = p.dt;
+    // TGS (solver_type 1, oracle substep_tgs): K position iterations of hs = dt / K on this step's
+    // factor and contact set; PGS: one step of hs = dt
+    const int K = TGS ? (p.solver_iterations < 1 ? 1 : (p.solver_iterations > kTgsMaxIt ? kTgsMaxIt : p.solver_iterations)) : 1;
+    const float hs = TGS ? dt / (float)K : dt;
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    kinematics<true>(L, m, lane, a.p, !first);
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    STAMP(PH_KINEMATICS);
+    body_forces(L, m, p, lane, mass_scale);
+    STAMP(PH_INERTIA_RNEA);
+    // ---- subtree sums: F_b (forces) and composite inertias, in place by body levels
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    subtree_levels<16, smpl::kNumBodyLevels - 2>(&L.F[0][0], &L.Ic[0][0], lane);
+    __builtin_amdgcn_s_setprio(kPrioDefault);
+    STAMP(PH_SUBTREE_SUMS);
+    drive_terms<TGS>(L, m, p, lane, hs);
+    STAMP(PH_DRIVES);
+    factor_free(L, m, lane, hs, st);
+    STAMP(PH_FACTOR);
+    if (!TGS && p.bias_midpoint) bias_midpoint(L, T, lane, p, st);
+    GeomPrefetch g;
+    prefetch_geometry(L, m, lane, g);
+    STAMP(PH_FREE_SOLVE);
+    // the previous solve's impulses (lane = row) before the self-pair list reuses L.lam as scratch
+    const float lam_prev = L.lam[lane];
+    const int nc = gen_contacts<TGS>(L, g, p, tkind, lane, st);
+    const int nr = build_rows(L, lane, nc);
+    STAMP(PH_CONTACT_GEN);
+    RowDesc rd;
+    row_setup(L, lane, nr, mu, lam_prev, rd);
+    const float damp = 1.0f / (1.0f + dt * p.angular_damping);
+    TgsStep ts{K, hs, damp, last, 0.f, 0.f};
+    if (nr > 0) {
+        RowSystem rsys;
+        row_system(L, T, p, a.full_dofs, lane, nr, hs, rd, rsys, st);
+        STAMP(PH_DELASSUS);
+        float lamv;
+        if constexpr (TGS) {
+            lamv = solve_tgs_rows(L, T, p, lane, nr, rd, rsys, ts, st);
+        } else {
+            lamv = solve_pgs(L, p, lane, nr, rd, rsys, st);
+            pgs_velocity(L, T, lane, rsys.z, lamv);
+        }
+        if (last) contact_forces_out(L, lane, nc, rd.act, lamv, dt);
     }
     if (nr == 0) {  // nothing to warm-start the next solve from
         L.lam[lane] = 0.f;
         if (lane == 0) L.nwc = 0;
     }
-    if (TGS && nr == 0) {  // TGS without contact rows: the iterations' drives and bias only
-        for (int it = 0; it < K; ++it) {
-            tgs_velocity(L, T, lane, 0.f, 0.f);
-            STAMP(11);
-            tgs_advance(it);
-        }
-        tgs_drive_out();
-    }
-    if (!TGS && nr == 0) {  // no contact: uf = u0 + L^-1 D^-1/2 yh
-        float yl = L.yh[lane] * L.sDinv[lane];
-        float y2 = lane < NH ? L.yh[64 + lane] * L.sDinv[64 + lane] : 0.f;
-        float r1[regla::kRowRegs], r2[regla::kRowRegs];
-        load_rows(L, T, lane, r1, r2);
-        solve_L(r1, r2, lane, yl, y2);
-        L.uf[lane] = L.u0[lane] + yl;
-        if (lane < NH) L.uf[64 + lane] = L.u0[64 + lane] + y2;
-        sync();
-    }
-    STAMP(11);
+    if (TGS && nr == 0) tgs_free_iterations(L, T, p, lane, ts, st);
+    if (!TGS && nr == 0) free_velocity(L, T, lane);
+    STAMP(PH_DU_SOLVE);
     if constexpr (TGS) {  // TGS: the iterations integrated the positions and set the drive force
-        STAMP(12);
+        STAMP(PH_INTEGRATE);
         return;
     }
-    // ---- drive force actually applied, damping, clamps, write velocities
-    if (last) {  // the reported drive force is the last substep's
-        for (int i = lane; i < NG; i += W)
-            if (i >= 6) L.dforce[i - 6] -= L.coef[i] * (L.uf[i] - L.u0[i]);
-        sync();
-        // plus the joint-limit force (dof_force = the joint's solver force, drive and limit together;
-        // oracle/he_oracle_physics.c): limit slot c (one per joint, row c) adds g lambda / dt over its
-        // joint's dofs, g = its row (kept in the contact-position words)
-        const int nl = __builtin_amdgcn_readfirstlane(L.nlim);
-        if (lane < nl && nr > 0) {
-            const int d0 = 3 * ((L.cbb[lane < MAXC ? lane : 0] & 0xFF) - 1);
-            const float lf = L.lam[lane] / dt;
-            L.dforce[d0] += L.cx[lane < MAXC ? lane : 0][0] * lf;
-            L.dforce[d0 + 1] += L.cx[lane < MAXC ? lane : 0][1] * lf;
-            L.dforce[d0 + 2] += L.cx[lane < MAXC ? lane : 0][2] * lf;
-        }
-        sync();
-    }
+    // ---- PGS: drive force actually applied, damping, clamps, write velocities
+    if (last) pgs_drive_out(L, lane, nr, dt);
     integrate_bodies(L, T, lane, p, dt, damp, L.uf, true, !last);
-    STAMP(12);
+    STAMP(PH_INTEGRATE);
+}
+
+// ---------------------------------------------------------------------------------- kernel body
+// body-level and per-dof tree tables into LDS (constant memory -> LDS once per launch)
+HE_DEV void load_tables(Lds& L, const PhysArgs& a, int lane) {
+    const he_model& m = *a.model;
+    if (lane < NB) {
+        const PhysTopo& T = *a.topo;
+        L.T.depth[lane] = T.body_depth[lane];
+        for (int k = 0; k < 9; ++k) L.T.chain[lane][k] = T.body_chain[lane][k];
+        L.T.dof0[lane] = T.body_dof0[lane];
+        L.T.anc_mask[lane] = T.anc_mask[lane];
+        L.T.sub_mask[lane] = T.sub_mask[lane];
+        L.T.jump4[lane] = kJump4.v[lane < NB ? lane : 0];
+        for (int c = 0; c < 3; ++c) L.T.local_pos[lane][c] = m.local_pos[lane][c];
+    }
+    L.T.cbody[lane] = a.topo->corner_body[lane];
+    for (int i = lane; i < NG; i += W) {
+        L.T.pack_start[i] = (int16_t)smpl::kPackStart[i];
+        L.T.dof_depth[i] = (int8_t)(smpl::kDofNanc[i] - 1);
+    }
+}
+
+// env e's root and dof rows into LDS, with the PD targets of this step (from the actions when given,
+// written back to dof_targets)
+HE_DEV void load_state(Lds& L, const PhysArgs& a, int e, int lane) {
+    const float* rs = a.root_states + (size_t)e * 13;
+    if (lane < 3) { L.root_pos[lane] = rs[lane]; L.u0[3 + lane] = rs[7 + lane]; L.u0[lane] = rs[10 + lane]; }
+    if (lane < 4) L.root_q[lane] = rs[3 + lane];
+    for (int d = lane; d < ND; d += W) {
+        L.q[d] = a.dof_state[((size_t)e * ND + d) * 2];
+        L.u0[6 + d] = a.dof_state[((size_t)e * ND + d) * 2 + 1];
+        float t;
+        if (a.actions) {  // humanoid_phc.py:1218-1228 + freeze :116-125
+            float act = a.actions[(size_t)e * ND + d];
+            if (a.clip_actions) act = fminf(fmaxf(act, -1.f), 1.f);
+            t = a.frozen[d] ? 0.f : a.pd_offset[d] + a.pd_scale[d] * act;
+            a.dof_targets[(size_t)e * ND + d] = t;
+        } else {
+            t = a.dof_targets[(size_t)e * ND + d];
+        }
+        L.tgt[d] = t;
+    }
+}
+
+// The warm-start cache (include/humanoid_engine.h HE_CACHE_WORDS): words 0..6 the root pose as a
+// signature, word 7 the row count, HE_CACHE_KEYS.. the 16-bit row keys (rows 2j / 2j + 1 in word j),
+// HE_CACHE_LAMBDA.. the impulses. Lane = word, then word W + lane.
+static_assert(HE_CACHE_KEYS + (MAXR + 1) / 2 <= HE_CACHE_LAMBDA && HE_CACHE_LAMBDA + MAXR <= HE_CACHE_WORDS &&
+              HE_CACHE_WORDS <= 2 * W && HE_CACHE_LAMBDA < W, "cache layout");
+// unpack into wckey / lam / nwc: valid while the root pose still equals the signature the previous
+// step wrote (an external write -- a reset -- breaks it)
+HE_DEV void cache_load(Lds& L, const PhysArgs& a, int e, int lane) {
+    const float* rs = a.root_states + (size_t)e * 13;
+    const float* cw = a.cache ? a.cache + (size_t)e * HE_CACHE_WORDS : nullptr;
+    const float w1 = cw ? cw[lane] : 0.f;
+    const float w2 = cw && lane < HE_CACHE_WORDS - W ? cw[W + (lane < HE_CACHE_WORDS - W ? lane : 0)] : 0.f;
+    const float sig = lane < 3 ? rs[lane] : (lane < 7 ? rs[lane < 7 ? lane : 0] : 0.f);
+    const bool diff = lane < 7 && __float_as_uint(w1) != __float_as_uint(sig);
+    const bool valid = cw && a.p.warm_start && __ballot(diff) == 0ull;
+    const int nw = valid ? __builtin_amdgcn_readlane(__float_as_int(w1), 7) : 0;
+    const int nwc = nw < 0 ? 0 : (nw > MAXR ? MAXR : nw);
+    constexpr int KW = (MAXR + 1) / 2;
+    if (lane >= HE_CACHE_KEYS && lane < HE_CACHE_KEYS + KW) {
+        const int j = lane - HE_CACHE_KEYS;
+        const uint32_t kw = __float_as_uint(w1);
+        L.wckey[2 * j] = (int)(kw & 0xFFFFu);
+        L.wckey[2 * j + 1] = (int)(kw >> 16);
+    }
+    // impulses: rows 0 .. W - HE_CACHE_LAMBDA - 1 from the first read, the rest from the second
+    if (lane >= HE_CACHE_LAMBDA) L.lam[lane - HE_CACHE_LAMBDA] = valid ? w1 : 0.f;
+    if (lane < HE_CACHE_LAMBDA) L.lam[W - HE_CACHE_LAMBDA + lane] = valid && W + lane < HE_CACHE_WORDS ? w2 : 0.f;
+    if (lane == 0) L.nwc = nwc;
+}
+// pack the last solve's rows: signature (the root pose just written), row count, row keys, impulses
+HE_DEV void cache_store(const Lds& L, const PhysArgs& a, int e, int lane) {
+    if (!a.cache) return;
+    float* cw = a.cache + (size_t)e * HE_CACHE_WORDS;
+    const int nwc = a.p.warm_start ? L.nwc : 0;
+    constexpr int KW = (MAXR + 1) / 2;
+    float v = 0.f;
+    if (lane < 3) v = L.root_pos[lane];
+    else if (lane < 7) v = L.root_q[lane < 7 ? lane - 3 : 0];
+    else if (lane == 7) v = __int_as_float(nwc);
+    else if (lane < HE_CACHE_KEYS + KW) {
+        const int j = lane - HE_CACHE_KEYS;
+        const uint32_t k0 = 2 * j < nwc ? (uint32_t)L.wckey[2 * j] & 0xFFFFu : 0u;
+        const uint32_t k1 = 2 * j + 1 < nwc ? (uint32_t)L.wckey[2 * j + 1] & 0xFFFFu : 0u;
+        v = __uint_as_float(k0 | (k1 << 16));
+    } else if (lane >= HE_CACHE_LAMBDA) v = lane - HE_CACHE_LAMBDA < nwc ? L.lam[lane - HE_CACHE_LAMBDA] : 0.f;
+    if (!a.p.warm_start) v = 0.f;
+    cw[lane] = v;
+    if (lane < HE_CACHE_WORDS - W) {
+        const int r = W - HE_CACHE_LAMBDA + lane;
+        cw[W + lane] = a.p.warm_start && r < nwc ? L.lam[r] : 0.f;
+    }
+}
+
+// env e's outputs from LDS after the final kinematics: generalized state, rigid-body rows (lane =
+// body), forces, contact counts. Returns the lane's body row (the fused epilogue reads its body from
+// the same registers).
+HE_DEV SimBody store_state(const Lds& L, const PhysArgs& a, int e, int lane) {
+    float* rso = a.root_states + (size_t)e * 13;
+    if (lane < 3) { rso[lane] = L.root_pos[lane]; rso[7 + lane] = L.u0[3 + lane]; rso[10 + lane] = L.u0[lane]; }
+    if (lane < 4) rso[3 + lane] = L.root_q[lane];
+    for (int d = lane; d < ND; d += W) {
+        a.dof_state[((size_t)e * ND + d) * 2] = L.q[d];
+        a.dof_state[((size_t)e * ND + d) * 2 + 1] = L.u0[6 + d];
+        a.dof_force[(size_t)e * ND + d] = L.dforce[d];
+    }
+    const SimBody sb = body_row(L, lane < NB ? lane : 0);
+    if (lane < NB) {
+        float* rb = a.rb_state + ((size_t)e * NB + lane) * 13;
+        rb[0] = sb.pos.x; rb[1] = sb.pos.y; rb[2] = sb.pos.z;
+        rb[3] = sb.rot.x; rb[4] = sb.rot.y; rb[5] = sb.rot.z; rb[6] = sb.rot.w;
+        rb[7] = sb.vel.x; rb[8] = sb.vel.y; rb[9] = sb.vel.z;
+        rb[10] = sb.ang.x; rb[11] = sb.ang.y; rb[12] = sb.ang.z;
+    }
+    for (int t = lane; t < NB * 3; t += W) a.contact_forces[(size_t)e * NB * 3 + t] = L.cf[t / 3][t % 3];
+    if (lane == 0 && a.num_contacts) a.num_contacts[e] = L.nc;
+    if (lane == 0 && a.dropped) a.dropped[e] = L.ncand - L.nc;
+    return sb;
 }
 
 // two waves per SIMD need at most 256 VGPRs + AGPRs. Unbounded, the allocator lands at 257 (one
@@ -2711,74 +2809,16 @@ HE_DEV void physics_body(const PhysArgs& a) {
     // in LDS for the epilogue (no registers held through the substeps)
     // The order is rebuilt on the launch stream (he_engine.cpp); an index outside [0, num_envs) (a
     // stray write into the buffer) falls back to workgroup id = env instead of faulting.
-    int e0 = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    if ((unsigned)e0 >= (unsigned)a.num_envs) e0 = (int)blockIdx.x;
-    int e = e0;
+    int e = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    if ((unsigned)e >= (unsigned)a.num_envs) e = (int)blockIdx.x;
     if (lane == 0) {
         L.sch_t0 = __builtin_readcyclecounter();
-        L.sch_e = e0;
+        L.sch_e = e;
     }
-    const he_model& m = *a.model;
-    // ---- body-level tree tables into LDS
-    if (lane < NB) {
-        const PhysTopo& T = *a.topo;
-        L.T.depth[lane] = T.body_depth[lane];
-        for (int k = 0; k < 9; ++k) L.T.chain[lane][k] = T.body_chain[lane][k];
-        L.T.dof0[lane] = T.body_dof0[lane];
-        L.T.anc_mask[lane] = T.anc_mask[lane];
-        L.T.sub_mask[lane] = T.sub_mask[lane];
-        L.T.jump4[lane] = kJump4.v[lane < NB ? lane : 0];
-        for (int c = 0; c < 3; ++c) L.T.local_pos[lane][c] = m.local_pos[lane][c];
-    }
-    L.T.cbody[lane] = a.topo->corner_body[lane];
-    for (int i = lane; i < NG; i += W) {  // per-dof tree tables (constant memory -> LDS once)
-        L.T.pack_start[i] = (int16_t)smpl::kPackStart[i];
-        L.T.dof_depth[i] = (int8_t)(smpl::kDofNanc[i] - 1);
-    }
-    // ---- load state
-    const float* rs = a.root_states + (size_t)e * 13;
-    if (lane < 3) { L.root_pos[lane] = rs[lane]; L.u0[3 + lane] = rs[7 + lane]; L.u0[lane] = rs[10 + lane]; }
-    if (lane < 4) L.root_q[lane] = rs[3 + lane];
-    for (int d = lane; d < ND; d += W) {
-        L.q[d] = a.dof_state[((size_t)e * ND + d) * 2];
-        L.u0[6 + d] = a.dof_state[((size_t)e * ND + d) * 2 + 1];
-        float t;
-        if (a.actions) {  // humanoid_phc.py:1218-1228 + freeze :116-125
-            float act = a.actions[(size_t)e * ND + d];
-            if (a.clip_actions) act = fminf(fmaxf(act, -1.f), 1.f);
-            t = a.frozen[d] ? 0.f : a.pd_offset[d] + a.pd_scale[d] * act;
-            a.dof_targets[(size_t)e * ND + d] = t;
-        } else {
-            t = a.dof_targets[(size_t)e * ND + d];
-        }
-        L.tgt[d] = t;
-    }
-    // ---- warm-start cache (include/humanoid_engine.h HE_CACHE_WORDS): valid while the root pose
-    // still equals the signature the previous step wrote (an external write -- a reset -- breaks it)
-    {
-        const float* cw = a.cache ? a.cache + (size_t)e * HE_CACHE_WORDS : nullptr;
-        const float w1 = cw ? cw[lane] : 0.f;
-        const float w2 = cw && lane < HE_CACHE_WORDS - W ? cw[W + (lane < HE_CACHE_WORDS - W ? lane : 0)] : 0.f;
-        const float sig = lane < 3 ? rs[lane] : (lane < 7 ? rs[lane < 7 ? lane : 0] : 0.f);
-        const bool diff = lane < 7 && __float_as_uint(w1) != __float_as_uint(sig);
-        const bool valid = cw && a.p.warm_start && __ballot(diff) == 0ull;
-        const int nw = valid ? __builtin_amdgcn_readlane(__float_as_int(w1), 7) : 0;
-        const int nwc = nw < 0 ? 0 : (nw > MAXR ? MAXR : nw);
-        // row keys: 16 bits each, rows 2j / 2j + 1 in word HE_CACHE_KEYS + j
-        constexpr int KW = (MAXR + 1) / 2;
-        if (lane >= HE_CACHE_KEYS && lane < HE_CACHE_KEYS + KW) {
-            const int j = lane - HE_CACHE_KEYS;
-            const uint32_t kw = __float_as_uint(w1);
-            L.wckey[2 * j] = (int)(kw & 0xFFFFu);
-            L.wckey[2 * j + 1] = (int)(kw >> 16);
-        }
-        // impulses: rows 0 .. W - HE_CACHE_LAMBDA - 1 from the first read, the rest from the second
-        if (lane >= HE_CACHE_LAMBDA) L.lam[lane - HE_CACHE_LAMBDA] = valid ? w1 : 0.f;
-        if (lane < HE_CACHE_LAMBDA) L.lam[W - HE_CACHE_LAMBDA + lane] = valid && W + lane < HE_CACHE_WORDS ? w2 : 0.f;
-        if (lane == 0) L.nwc = nwc;
-    }
-    static_assert(HE_CACHE_KEYS + (MAXR + 1) / 2 <= HE_CACHE_LAMBDA && HE_CACHE_LAMBDA + MAXR <= HE_CACHE_WORDS &&
-                  HE_CACHE_WORDS <= 2 * W && HE_CACHE_LAMBDA < W, "cache layout");
+    // ---- tables, state, warm-start cache
+    load_tables(L, a, lane);
+    load_state(L, a, e, lane);
+    cache_load(L, a, e, lane);
     if (a.fused && lane == 0) {  // fused imitation: bookkeeping + motion metadata (trips 1, 2) now
         const ImitArgs& im = a.im;
         const int64_t mid = clamp_mid(im.m, im.motion_ids[e]);
@@ -2797,10 +2837,10 @@ HE_DEV void physics_body(const PhysArgs& a) {
     const float* ms = a.mass_scale ? a.mass_scale + (size_t)e * NB : nullptr;
     float mu = a.friction ? a.friction[e] : a.p.friction;
     int tk = (a.p.terrain && a.terrain_kind) ? a.terrain_kind[e] : 0;
-    unsigned long long* stamps = a.stamps ? a.stamps + (size_t)e * HE_STAMP_SLOTS : nullptr;
-    unsigned long long t_prev = __builtin_readcyclecounter();
+    Stamps st{a.stamps ? a.stamps + (size_t)e * HE_STAMP_SLOTS : nullptr, __builtin_readcyclecounter()};
+    // ---- substeps
     for (int s = 0; s < a.substeps; ++s)
-        substep<TGS>(L, a, a.model, lane, ms, mu, tk, stamps, t_prev, s == 0, s == a.substeps - 1);
+        substep<TGS>(L, a, a.model, lane, ms, mu, tk, st, s == 0, s == a.substeps - 1);
     // ---- fused imitation (he_env_step): the reference samples depend only on the env's motion
     // bookkeeping (read into LDS at the kernel's start), so their loads are issued here and land
     // behind the final kinematics and stores
@@ -2813,28 +2853,9 @@ HE_DEV void physics_body(const PhysArgs& a) {
     }
     // ---- outputs: generalized state, FK rigid-body state, forces
     e = L.sch_e;  // from LDS: not held through the substeps
-    kinematics<false>(L, m, lane, a.p, a.substeps > 0);
-    STAMP(13);
-    float* rso = a.root_states + (size_t)e * 13;
-    if (lane < 3) { rso[lane] = L.root_pos[lane]; rso[7 + lane] = L.u0[3 + lane]; rso[10 + lane] = L.u0[lane]; }
-    if (lane < 4) rso[3 + lane] = L.root_q[lane];
-    for (int d = lane; d < ND; d += W) {
-        a.dof_state[((size_t)e * ND + d) * 2] = L.q[d];
-        a.dof_state[((size_t)e * ND + d) * 2 + 1] = L.u0[6 + d];
-        a.dof_force[(size_t)e * ND + d] = L.dforce[d];
-    }
-    // rigid-body rows, lane = body (the fused epilogue reads its body from the same registers)
-    SimBody sb = body_row(L, lane < NB ? lane : 0);
-    if (lane < NB) {
-        float* rb = a.rb_state + ((size_t)e * NB + lane) * 13;
-        rb[0] = sb.pos.x; rb[1] = sb.pos.y; rb[2] = sb.pos.z;
-        rb[3] = sb.rot.x; rb[4] = sb.rot.y; rb[5] = sb.rot.z; rb[6] = sb.rot.w;
-        rb[7] = sb.vel.x; rb[8] = sb.vel.y; rb[9] = sb.vel.z;
-        rb[10] = sb.ang.x; rb[11] = sb.ang.y; rb[12] = sb.ang.z;
-    }
-    for (int t = lane; t < NB * 3; t += W) a.contact_forces[(size_t)e * NB * 3 + t] = L.cf[t / 3][t % 3];
-    if (lane == 0 && a.num_contacts) a.num_contacts[e] = L.nc;
-    if (lane == 0 && a.dropped) a.dropped[e] = L.ncand - L.nc;
+    kinematics<false>(L, *a.model, lane, a.p, a.substeps > 0);
+    STAMP(PH_FINAL_FK);
+    const SimBody sb = store_state(L, a, e, lane);
     if (a.fused && lane < GROUP) {
         // he_env_step: the imitation step of this env on lanes 0..31 (lane = body), after every
         // physics store above has landed (a fused reset overwrites those rows)
@@ -2844,28 +2865,8 @@ HE_DEV void physics_body(const PhysArgs& a) {
             pw = power_term(&L.dforce[3 * lane], &L.u0[6 + 3 * lane], 1);
         imitation_finish<false>(a.im, e, e, lane, lane == 0, imitation_frames_blend(iraw), sb, pw);
     }
-    STAMP(24);
-    if (a.cache) {  // signature (the root pose just written), row count, row keys, impulses
-        float* cw = a.cache + (size_t)e * HE_CACHE_WORDS;
-        const int nwc = a.p.warm_start ? L.nwc : 0;
-        constexpr int KW = (MAXR + 1) / 2;
-        float v = 0.f;
-        if (lane < 3) v = L.root_pos[lane];
-        else if (lane < 7) v = L.root_q[lane < 7 ? lane - 3 : 0];
-        else if (lane == 7) v = __int_as_float(nwc);
-        else if (lane < HE_CACHE_KEYS + KW) {
-            const int j = lane - HE_CACHE_KEYS;
-            const uint32_t k0 = 2 * j < nwc ? (uint32_t)L.wckey[2 * j] & 0xFFFFu : 0u;
-            const uint32_t k1 = 2 * j + 1 < nwc ? (uint32_t)L.wckey[2 * j + 1] & 0xFFFFu : 0u;
-            v = __uint_as_float(k0 | (k1 << 16));
-        } else if (lane >= HE_CACHE_LAMBDA) v = lane - HE_CACHE_LAMBDA < nwc ? L.lam[lane - HE_CACHE_LAMBDA] : 0.f;
-        if (!a.p.warm_start) v = 0.f;
-        cw[lane] = v;
-        if (lane < HE_CACHE_WORDS - W) {
-            const int r = W - HE_CACHE_LAMBDA + lane;
-            cw[W + lane] = a.p.warm_start && r < nwc ? L.lam[r] : 0.f;
-        }
-    }
+    STAMP(PH_FUSED);
+    cache_store(L, a, e, lane);
     if (a.cost && lane == 0) {  // this env's cycles, for the next launch's order
         const unsigned long long cyc = __builtin_readcyclecounter() - L.sch_t0;
         a.cost[e] = cyc > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cyc;
@@ -2880,10 +2881,7 @@ __global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs(PhysArgs 
 }  // namespace
 
 static_assert(sizeof(Lds) <= 20480, "two workgroups per SIMD (8 per CU) need <= 20 KB of LDS each");
-#ifndef HE_LDS_EXTRA  // diagnostics only: extra dynamic LDS per wave, to run fewer waves per CU
-#define HE_LDS_EXTRA 0   // (one wave alone on its CU; round 4)
-#endif
-size_t physics_lds_bytes() { return (sizeof(Lds) + 15) / 16 * 16 + HE_LDS_EXTRA; }
+size_t physics_lds_bytes() { return (sizeof(Lds) + 15) / 16 * 16; }
 
 bool physics_phase_stamps() { return HE_PHASE_STAMPS != 0; }
 
@@ -3015,7 +3013,6 @@ hipError_t warm_physics_kernels(hipStream_t stream, int mode) {
     physics_order_kernel<<<1, kOrderThreads, 0, stream>>>(nullptr, nullptr, 0);
     return hipGetLastError();
 }
-
 
 hipError_t launch_physics_order(const uint32_t* cost, int32_t* order, int num_envs, hipStream_t stream) {
     if (num_envs <= 0) return hipSuccess;
