@@ -40,6 +40,14 @@ def key_fields(key):
     key = int(key)
     return key & 31, ((key >> 5) & 31) - 2, (key >> 10) & 15, key >> 14
 DTYPE_F32, DTYPE_I32 = 1, 2
+# include/humanoid_engine.h HE_SPACE_* (gymapi.CoordinateSpace): the frame of he_apply_body_forces' vectors
+SPACE_ENV, SPACE_LOCAL, SPACE_GLOBAL = 0, 1, 2
+# prototypes of the external-wrench entry points (argument types after the int return):
+# (engine, force, torque | pos, space, hold, stream)
+FORCE_PROTOTYPES = {
+    "he_apply_body_forces": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "he_apply_body_forces_at_pos": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+}
 
 
 class HeModel(C.Structure):

@@ -27,6 +27,7 @@ SOURCES = [
     ("he_physics.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize",
                         "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
     ("he_ingest.hip", []),
+    ("he_forces.hip", []),
     ("he_rollout.hip", ["-ffp-contract=off"]),  # GAE: the Cython module's float32 rounding
     ("he_engine.cpp", ["-x", "hip"]),
 ]

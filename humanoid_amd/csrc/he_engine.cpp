@@ -102,6 +102,11 @@ struct he_engine {
     long long order_seq = 0;          // rebuilds issued
     long long order_seen_seq = -1;    // the rebuild the last physics launch waited for, on ...
     hipStream_t order_seen_stream = nullptr;  // ... this stream
+    // external wrenches (he_apply_body_forces): the [N,24,6] world-axis (torque, force at the CoM) rows
+    // and the gym.simulate() calls they still act in (0: nothing pending; the rows are then overwritten
+    // by the next call, not accumulated into)
+    float* wrench = nullptr;
+    int wrench_hold = 0;
 };
 
 extern "C" {
@@ -232,6 +237,8 @@ int he_create_envs(he_engine* h, int num_envs, const float* host_start_xy) {
     HE_CHECK(hipMemcpy(h->order, ord.data(), ord.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HE_CHECK(dalloc(&h->cost, (size_t)N));
     HE_CHECK(hipMemset(h->cost, 0, (size_t)N * sizeof(uint32_t)));
+    HE_CHECK(dalloc(&h->wrench, (size_t)N * HE_NUM_BODIES * 6));
+    HE_CHECK(hipMemset(h->wrench, 0, (size_t)N * HE_NUM_BODIES * 6 * sizeof(float)));
     if (const char* v = std::getenv("HE_PHYS_ORDER")) h->order_every = std::atoi(v);
     if (const char* v = std::getenv("HE_TGS_LEGS")) h->full_dofs = std::atoi(v) == 0;
     h->num_envs = N;
@@ -243,7 +250,7 @@ int he_destroy(he_engine* h) {
     hipSetDevice(h->device);
     void* ptrs[] = {h->d_model, h->d_topo, h->root, h->dof_state, h->rb, h->cf, h->dof_force, h->targets,
                     h->num_contacts, h->dropped, h->cache, h->init_root, h->meta_cache, h->d_rest, h->pd_offset, h->pd_scale, h->frozen, h->m_hot, h->m_cold, h->m_lengths,
-                    h->m_dt, h->m_starts, h->m_nframes, h->order, h->cost};
+                    h->m_dt, h->m_starts, h->m_nframes, h->order, h->cost, h->wrench};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (h->order_ready) hipEventDestroy(h->order_ready);
@@ -325,6 +332,7 @@ static int warm_kernels(int device) {
     HE_CHECK(warm_physics_kernels(nullptr, wm));
     HE_CHECK(warm_imitation_kernels(nullptr, wm));
     HE_CHECK(warm_ingest_kernels(nullptr, wm));
+    HE_CHECK(warm_forces_kernels(nullptr, wm));
     HE_CHECK(hipDeviceSynchronize());
     warmed[device] = true;
     return 0;
@@ -401,9 +409,50 @@ static PhysArgs phys_args(he_engine* h, int num_simulate, const float* actions) 
     a.order = ordered ? h->order : nullptr;
     a.cost = ordered ? h->cost : nullptr;
     a.full_dofs = h->full_dofs;
+    // a pending wrench covers the launch's leading gym.simulate() calls, as many as its hold has left
+    if (h->wrench_hold > 0) {
+        const int cover = h->wrench_hold < num_simulate ? h->wrench_hold : num_simulate;
+        a.ext_wrench = h->wrench;
+        a.ext_steps = cover * h->params.substeps;
+        h->wrench_hold -= cover;
+    }
     return a;
 }
+
+static int apply_wrench(he_engine* h, const float* force, const float* second, int at_pos, int space, int hold,
+                        void* stream, const char* what) {
+    if (!h) return fail("%s: null handle", what);
+    if (!h->num_envs) return fail("%s: no envs created", what);
+    if (space != HE_SPACE_ENV && space != HE_SPACE_LOCAL && space != HE_SPACE_GLOBAL)
+        return fail("%s: space must be HE_SPACE_ENV (0), HE_SPACE_LOCAL (1) or HE_SPACE_GLOBAL (2), got %d", what, space);
+    if (hold < 1) return fail("%s: hold must be >= 1 (gym.simulate() calls), got %d", what, hold);
+    if (at_pos && (!force || !second)) return fail("%s: force and pos must both be given", what);
+    if (!force && !second) {  // clear
+        h->wrench_hold = 0;
+        return 0;
+    }
+    WrenchArgs a{};
+    a.force = force;
+    a.second = second;
+    a.rb_state = h->rb;
+    a.model = h->d_model;
+    a.wrench = h->wrench;
+    a.rows = h->num_envs * HE_NUM_BODIES;
+    a.space = space;
+    a.at_pos = at_pos;
+    a.accumulate = h->wrench_hold > 0;
+    HE_CHECK(launch_body_wrench(a, (hipStream_t)stream));
+    h->wrench_hold = hold;
+    return 0;
+}
 }  // namespace
+
+int he_apply_body_forces(he_engine* h, const float* force, const float* torque, int space, int hold, void* stream) {
+    return apply_wrench(h, force, torque, 0, space, hold, stream, "he_apply_body_forces");
+}
+int he_apply_body_forces_at_pos(he_engine* h, const float* force, const float* pos, int space, int hold, void* stream) {
+    return apply_wrench(h, force, pos, 1, space, hold, stream, "he_apply_body_forces_at_pos");
+}
 
 // the physics launch, then every order_every launches the next launches' dispatch order from this
 // one's per-env cycles (heavy envs first, he_kernels.h launch_physics_order)

@@ -115,7 +115,29 @@ struct PhysArgs {
     int fused;                   // 1: the imitation step (mode 1) runs in the epilogue (he_env_step)
     int full_dofs;               // 1: no leg class (every env's Zh products over 75 dofs; HE_TGS_LEGS=0, tests)
     ImitArgs im;                 // its arguments when fused
+    // external wrenches (he_apply_body_forces): the engine's [N,24,6] world-axis (torque, force at the
+    // CoM) rows and the number of leading physics steps of this launch they act in; null / 0: none
+    // pending, and launch_physics runs the kernels without the wrench code
+    const float* ext_wrench;
+    int ext_steps;
 };
+
+// he_apply_body_forces / he_apply_body_forces_at_pos: (force, torque | application point, space) and
+// the bodies' current rigid-body rows into the [N*24,6] (torque, force) rows of `wrench`, in world
+// axes about each body's CoM; accumulate 0 overwrites the rows, 1 adds to them. force / second may
+// be null (at_pos: both given).
+struct WrenchArgs {
+    const float* force;      // [N*24,3] or null
+    const float* second;     // [N*24,3] torque, or the application point when at_pos, or null
+    const float* rb_state;   // [N*24,13]
+    const he_model* model;   // device copy (the bodies' CoM offsets)
+    float* wrench;           // [N*24,6]
+    int rows;                // N*24
+    int space;               // HE_SPACE_*
+    int at_pos;
+    int accumulate;
+};
+hipError_t launch_body_wrench(const WrenchArgs& a, hipStream_t stream);
 
 hipError_t launch_imitation(const ImitArgs& a, hipStream_t stream);
 hipError_t launch_amp(const AmpArgs& a, hipStream_t stream);
@@ -139,6 +161,7 @@ hipError_t launch_physics_order(const uint32_t* cost, int32_t* order, int num_en
 hipError_t warm_imitation_kernels(hipStream_t stream, int mode);
 hipError_t warm_physics_kernels(hipStream_t stream, int mode);
 hipError_t warm_ingest_kernels(hipStream_t stream, int mode);
+hipError_t warm_forces_kernels(hipStream_t stream, int mode);
 bool physics_phase_stamps();  // built with HE_PHASE_STAMPS (diagnostic twin library)
 hipError_t launch_ingest(const float* pose, const float* trans, const int32_t* parents, const float* local_pos,
                          const int64_t* starts, const int64_t* nframes, const float* dt, int num_clips, int64_t F,

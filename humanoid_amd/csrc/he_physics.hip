@@ -90,6 +90,7 @@ struct Lds {
     int8_t srow0[MAXC];            // first solver row of each slot
     int8_t rslot[W], rkind[W];     // solver row -> its slot, its kind (0 normal / limit, 1 2 tangential, 3 torsional)
     BodyTopo T;
+    float Q[NG];  // external wrenches' generalized force of this physics step (ext_wrench_terms; the EXT kernels only)
 };
 
 // wave priority: s_setprio 3 over the serial chains (PGS rows, the elimination, the L^-T sweeps;
@@ -1454,7 +1455,8 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
 //        impulses
 //   Ic / Ib  composite / own inertias; from terrain_candidates to the end of gen_contacts the bodies'
 //        world segments live in Ib (PGS) or Ic (TGS: Ib keeps the own inertias for tgs_bias_at)
-//   Acc  RNEA accelerations until body_forces; the midpoint's body forces; from terrain_candidates the
+//   Acc  RNEA accelerations until body_forces; the external wrenches' subtree sums (ext_wrench_terms,
+//        the EXT kernels); the midpoint's body forces; from terrain_candidates the
 //        bounding spheres (bsph) and, after them, build_rows' patch radii (patch_radius), both dead
 //        after row_setup; then tgs_bias_at's body forces
 //   F    subtree forces until bias_midpoint's correction; build_rows' patch normals and centroids
@@ -1499,19 +1501,50 @@ HE_DEV void body_forces(Lds& L, const he_model& m, const he_sim_params& p, int l
     sync();
 }
 
+// External wrenches (he_apply_body_forces; the EXT kernels only), after the subtree sums: body b's
+// (torque, force at the CoM) row becomes the spatial wrench about o, W_b = (tau_b + s_b x f_b, f_b) with
+// s_b the CoM about o as body_forces forms it, so the force follows the body from step to step; the
+// subtree sums by body levels; Q_i = S_i . sum_subtree(body(i)) W into L.Q. Acc is scratch (dead from
+// body_forces to the midpoint bias / the contact phase). on == false (the launch's physics steps past
+// the wrench's hold): Q = 0, and the step computes what the kernels without the wrench code compute.
+HE_DEV void ext_wrench_terms(Lds& L, const he_model& m, const PhysArgs& a, int lane, bool on) {
+    if (!on) {  // wave-uniform
+        L.Q[lane] = 0.f;
+        if (lane < NG - W) L.Q[W + lane] = 0.f;
+        sync();
+        return;
+    }
+    if (lane < NB) {
+        const int b = lane;
+        const float* w = a.ext_wrench + ((size_t)L.sch_e * NB + b) * 6;  // the env from LDS: no register held
+        const f3 tq = f3{w[0], w[1], w[2]}, f = f3{w[3], w[4], w[5]};
+        const f4 q = f4{L.qw[b][0], L.qw[b][1], L.qw[b][2], L.qw[b][3]};
+        const f3 s = f3{L.pw[b][0], L.pw[b][1], L.pw[b][2]} + qapply(q, f3{m.com[b][0], m.com[b][1], m.com[b][2]});
+        const f3 n = tq + cross3(s, f);
+        L.Acc[b][0] = n.x; L.Acc[b][1] = n.y; L.Acc[b][2] = n.z;
+        L.Acc[b][3] = f.x; L.Acc[b][4] = f.y; L.Acc[b][5] = f.z;
+    }
+    sync();
+    subtree_levels<6, smpl::kNumBodyLevels - 2>(&L.Acc[0][0], nullptr, lane);
+    L.Q[lane] = dot6(L.S[lane], L.Acc[dof_body(lane)]);
+    if (lane < NG - W) L.Q[W + lane] = dot6(L.S[W + lane], L.Acc[(W + lane - 6) / 3 + 1]);
+    sync();
+}
+
 // Bias forces, IS_i = Ic S_i and the implicit PD drives (oracle: the drive block), lane = dof, then
 // dofs 64..74 on lanes 0..10. Writes IS, dforce (PGS: the drive torque; TGS: the scaled stiffness),
 // uf (TGS: the bias at u0), rhs, coef. The per-dof body stays a lambda that captures by reference:
 // as a function taking hs and limmask by value, the PGS kernel came out with one v_fma and one v_mul
 // fewer and one v_sub more (a product contracted another way), and its results left the parent's bits.
-template <bool TGS>
+template <bool TGS, bool EXT>
 HE_DEV void drive_terms(Lds& L, const he_model& m, const he_sim_params& p, int lane, float hs) {
     const uint32_t limmask = p.joint_limits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)L.limmask) : 0u;
     // lane = dof (then dofs 64..74 on lanes 0..10), the root's six dofs selected out: no loop,
     // no root branch, saturation by selects
     auto dof_terms = [&](int i, bool may_root) {
         const int b = may_root ? dof_body(i) : (i - 6) / 3 + 1;
-        const float bias = dot6(L.S[i], L.F[b]);
+        float bias = dot6(L.S[i], L.F[b]);
+        if constexpr (EXT) bias -= L.Q[i];  // an external wrench enters as a bias of the opposite sign
         si_apply(L.Ic[b], L.S[i], L.IS[i]);
         const bool jd = !may_root || i >= 6;
         const int d = jd ? i - 6 : 0;
@@ -2267,6 +2300,7 @@ struct TgsStep {
 // What follows a position iteration's velocity update: its drive torques, the positions by hs (the
 // last iteration: the step's output velocity), then (not the last) the next iteration's bias and
 // free motion
+template <bool EXT>
 HE_DEV void tgs_advance(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int it, TgsStep& ts, Stamps& st) {
     const bool lastit = it + 1 == ts.K;
     tgs_drive_acc(L, lane, ts.tf1, ts.tf2);
@@ -2279,6 +2313,10 @@ HE_DEV void tgs_advance(Lds& L, const BodyTopo& T, const he_sim_params& p, int l
         if (p.bias_midpoint && ((it + 1) % kTgsBiasEvery) == 0) {
             float b1, b2;
             tgs_bias_at(L, T, lane, p, L.u0, b1, b2);
+            if constexpr (EXT) {  // the step's kinematics are frozen: Q holds over the iterations
+                b1 -= L.Q[lane];
+                if (lane < regla::NH) b2 -= L.Q[64 + lane];
+            }
             L.uf[lane] = b1;
             if (lane < regla::NH) L.uf[64 + lane] = b2;
         }
@@ -2316,7 +2354,7 @@ HE_DEV void tgs_drive_out(Lds& L, int lane, const TgsStep& ts) {
 // are exact zeros. Precondition: NC == 32 (no row sits on lanes 32..63), and every lane >= nr
 // carries dl == 0 (its `act` is false) with a finite z, so that its products are +-0 and not NaN.
 // A change to how the inactive lanes are handled has to keep both.
-template <int NC>
+template <int NC, bool EXT>
 HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
                        const RowSystem& s, int nrb, float g0, float w0, TgsStep& ts, Stamps& st) {
     using regla::NH;
@@ -2383,7 +2421,7 @@ HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int la
         STAMP(PH_DU_SOLVE);
         if (isn) sep += hs * v;
         const bool lastit = it + 1 == ts.K;
-        tgs_advance(L, T, p, lane, it, ts, st);
+        tgs_advance<EXT>(L, T, p, lane, it, ts, st);
         __builtin_amdgcn_sched_barrier(0);
         if (!lastit) {
             // the next sweep's start about lambda = applied + dl: w = J u + zh . yh + bias(sep) + A dl,
@@ -2411,6 +2449,7 @@ HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int la
 // impulses' per-iteration share g0, its residual w = brow + A g0; then the iterations by row-count
 // class; the cache and the reported forces take the step's accumulated impulses. Writes lam, nwc,
 // dforce (drive and joint-limit force).
+template <bool EXT>
 HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
                             const RowSystem& s, TgsStep& ts, Stamps& st) {
     const int nrb = __builtin_amdgcn_readfirstlane(nr);
@@ -2418,8 +2457,8 @@ HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, i
     float w0 = s.brow;
     if (__ballot(g0 != 0.f)) w0 += warm_residual(s.acol, g0, nrb);  // wave-uniform
     float lamv;
-    if (nrb <= 32) lamv = solve_tgs<32>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
-    else lamv = solve_tgs<MAXR>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
+    if (nrb <= 32) lamv = solve_tgs<32, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
+    else lamv = solve_tgs<MAXR, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
     L.lam[lane] = r.act ? lamv : 0.f;
     if (lane == 0) L.nwc = p.warm_start ? nr : 0;
     tgs_drive_out(L, lane, ts);
@@ -2428,11 +2467,12 @@ HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, i
     return lamv;
 }
 // TGS without contact rows: the iterations' drives and bias only
+template <bool EXT>
 HE_DEV void tgs_free_iterations(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, TgsStep& ts, Stamps& st) {
     for (int it = 0; it < ts.K; ++it) {
         tgs_velocity(L, T, lane, 0.f, 0.f);
         STAMP(PH_DU_SOLVE);
-        tgs_advance(L, T, p, lane, it, ts, st);
+        tgs_advance<EXT>(L, T, p, lane, it, ts, st);
     }
     tgs_drive_out(L, lane, ts);
 }
@@ -2580,9 +2620,9 @@ HE_DEV void contact_forces_out(Lds& L, int lane, int nc, bool act, float lamv, f
 }
 
 // ---------------------------------------------------------------------------------- one substep
-template <bool TGS>
+template <bool TGS, bool EXT>
 HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
-                    const float* mass_scale, float mu, int tkind, Stamps& st, bool first, bool last) {
+                    const float* mass_scale, float mu, int tkind, Stamps& st, bool first, bool last, bool ext_on) {
     // the launch arguments through an opaque offset too: their fields are re-read (scalar loads
     // from the kernarg segment) where used instead of being held in SGPRs across the substep loop
     int ao = 0;
@@ -2621,7 +2661,8 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     subtree_levels<16, smpl::kNumBodyLevels - 2>(&L.F[0][0], &L.Ic[0][0], lane);
     __builtin_amdgcn_s_setprio(kPrioDefault);
     STAMP(PH_SUBTREE_SUMS);
-    drive_terms<TGS>(L, m, p, lane, hs);
+    if constexpr (EXT) ext_wrench_terms(L, m, a, lane, ext_on);
+    drive_terms<TGS, EXT>(L, m, p, lane, hs);
     STAMP(PH_DRIVES);
     factor_free(L, m, lane, hs, st);
     STAMP(PH_FACTOR);
@@ -2644,7 +2685,7 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
         STAMP(PH_DELASSUS);
         float lamv;
         if constexpr (TGS) {
-            lamv = solve_tgs_rows(L, T, p, lane, nr, rd, rsys, ts, st);
+            lamv = solve_tgs_rows<EXT>(L, T, p, lane, nr, rd, rsys, ts, st);
         } else {
             lamv = solve_pgs(L, p, lane, nr, rd, rsys, st);
             pgs_velocity(L, T, lane, rsys.z, lamv);
@@ -2655,7 +2696,7 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
         L.lam[lane] = 0.f;
         if (lane == 0) L.nwc = 0;
     }
-    if (TGS && nr == 0) tgs_free_iterations(L, T, p, lane, ts, st);
+    if (TGS && nr == 0) tgs_free_iterations<EXT>(L, T, p, lane, ts, st);
     if (!TGS && nr == 0) free_velocity(L, T, lane);
     STAMP(PH_DU_SOLVE);
     if constexpr (TGS) {  // TGS: the iterations integrated the positions and set the drive force
@@ -2799,7 +2840,7 @@ HE_DEV SimBody store_state(const Lds& L, const PhysArgs& a, int e, int lane) {
 #ifndef HE_MIN_WAVES
 #define HE_MIN_WAVES 2
 #endif
-template <bool TGS>
+template <bool TGS, bool EXT>
 HE_DEV void physics_body(const PhysArgs& a) {
     extern __shared__ float smem[];
     Lds& L = *reinterpret_cast<Lds*>(smem);
@@ -2839,8 +2880,14 @@ HE_DEV void physics_body(const PhysArgs& a) {
     int tk = (a.p.terrain && a.terrain_kind) ? a.terrain_kind[e] : 0;
     Stamps st{a.stamps ? a.stamps + (size_t)e * HE_STAMP_SLOTS : nullptr, __builtin_readcyclecounter()};
     // ---- substeps
-    for (int s = 0; s < a.substeps; ++s)
-        substep<TGS>(L, a, a.model, lane, ms, mu, tk, st, s == 0, s == a.substeps - 1);
+    for (int s = 0; s < a.substeps; ++s) {
+        // EXT: the wrench acts in the launch's leading ext_steps physics steps. The step at which its
+        // hold ends starts as a launch's first step does (the joints' rotations from their angles, not
+        // the integrator's cached ones), so one launch over the end of a hold gives the bits of two
+        // launches split there.
+        const bool first = EXT ? s == 0 || s == a.ext_steps : s == 0;
+        substep<TGS, EXT>(L, a, a.model, lane, ms, mu, tk, st, first, s == a.substeps - 1, EXT && s < a.ext_steps);
+    }
     // ---- fused imitation (he_env_step): the reference samples depend only on the env's motion
     // bookkeeping (read into LDS at the kernel's start), so their loads are issued here and land
     // behind the final kinematics and stores
@@ -2875,8 +2922,12 @@ HE_DEV void physics_body(const PhysArgs& a) {
 
 // he_sim_params.solver_type 0 (PGS) and 1 (TGS): one instantiation each, so that the TGS iterations'
 // register plan does not touch the PGS kernel's
-__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel(PhysArgs a) { physics_body<false>(a); }
-__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs(PhysArgs a) { physics_body<true>(a); }
+__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel(PhysArgs a) { physics_body<false, false>(a); }
+__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs(PhysArgs a) { physics_body<true, false>(a); }
+// the same steps with external wrenches (PhysArgs.ext_wrench, he_apply_body_forces): launched only while
+// a wrench is pending, so every other launch runs the two kernels above unchanged
+__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_ext(PhysArgs a) { physics_body<false, true>(a); }
+__global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs_ext(PhysArgs a) { physics_body<true, true>(a); }
 
 }  // namespace
 
@@ -3010,6 +3061,10 @@ hipError_t warm_physics_kernels(hipStream_t stream, int mode) {
     HE_RETURN_IF(hipGetLastError());
     physics_kernel_tgs<<<1, W, physics_lds_bytes(), stream>>>(pa);
     HE_RETURN_IF(hipGetLastError());
+    physics_kernel_ext<<<1, W, physics_lds_bytes(), stream>>>(pa);
+    HE_RETURN_IF(hipGetLastError());
+    physics_kernel_tgs_ext<<<1, W, physics_lds_bytes(), stream>>>(pa);
+    HE_RETURN_IF(hipGetLastError());
     physics_order_kernel<<<1, kOrderThreads, 0, stream>>>(nullptr, nullptr, 0);
     return hipGetLastError();
 }
@@ -3023,7 +3078,10 @@ hipError_t launch_physics_order(const uint32_t* cost, int32_t* order, int num_en
 hipError_t launch_physics(const PhysArgs& a, hipStream_t stream) {
     if (a.num_envs <= 0) return hipSuccess;
     const size_t lds = physics_lds_bytes();
-    if (a.p.solver_type == 1) physics_kernel_tgs<<<a.num_envs, W, lds, stream>>>(a);
+    const bool ext = a.ext_wrench && a.ext_steps > 0;  // a wrench pending for this launch
+    if (ext && a.p.solver_type == 1) physics_kernel_tgs_ext<<<a.num_envs, W, lds, stream>>>(a);
+    else if (ext) physics_kernel_ext<<<a.num_envs, W, lds, stream>>>(a);
+    else if (a.p.solver_type == 1) physics_kernel_tgs<<<a.num_envs, W, lds, stream>>>(a);
     else physics_kernel<<<a.num_envs, W, lds, stream>>>(a);
     return hipGetLastError();
 }

@@ -31,7 +31,7 @@ HE_SYMBOLS = (
     "he_set_dof_targets_indexed", "he_set_env_properties", "he_simulate", "he_set_pd_params", "he_step_actions",
     "he_refresh", "he_load_motions", "he_imitation_step", "he_motion_state", "he_reset_envs", "he_env_step",
     "he_imitation_reset_step", "he_set_debug_stamps", "he_hash_uniform", "he_ingest_clips", "he_set_eval",
-    "he_set_amp", "he_amp_observations", "he_set_fused_step",
+    "he_set_amp", "he_amp_observations", "he_set_fused_step", "he_apply_body_forces", "he_apply_body_forces_at_pos",
     # include/humanoid_rollout.h
     "he_rollout_store", "he_rollout_order", "he_rollout_gather", "he_gae", "he_gae_minibatch", "he_episode_step",
 )
@@ -78,6 +78,7 @@ def load_library(path: Optional[str] = None):
         "he_gae_minibatch": [V, V, V, V, V, C.c_int64, F, F, C.c_int32, C.c_int32, C.c_int32, V, V, V],
         "he_episode_step": [C.c_int32] + [V] * 14,
     }
+    sigs.update(_abi.FORCE_PROTOTYPES)
     for name, args in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -286,6 +287,33 @@ class Engine:
         import torch
         a = self._contig(actions, torch.float32)
         _check(self.lib.he_step_actions(self.h, C.c_void_p(a.data_ptr()), int(num_simulate), self.stream))
+
+    # ------------------------------------------------------------------ external wrenches
+    def _body_rows(self, t, what):
+        import torch
+        if t is None:
+            return None
+        t = self._contig(t, torch.float32)
+        if tuple(t.shape) not in ((self.num_envs, _abi.NB, 3), (self.num_envs * _abi.NB, 3)):
+            raise EngineError(f"{what} must be [num_envs,24,3] or [num_envs*24,3], got {tuple(t.shape)}")
+        return C.c_void_p(t.data_ptr())
+
+    def apply_body_forces(self, force=None, torque=None, space: int = _abi.SPACE_ENV, hold: int = 1):
+        """gym.apply_rigid_body_force_tensors: forces (at the bodies' centres of mass) and torques,
+        [N,24,3] or [N*24,3] in `space` (_abi.SPACE_*), acting during the next `hold` simulate() calls.
+        Calls before the next physics launch accumulate; both None clears (clear_body_forces)."""
+        _check(self.lib.he_apply_body_forces(self.h, self._body_rows(force, "force"), self._body_rows(torque, "torque"),
+                                             int(space), int(hold), self.stream))
+
+    def apply_body_forces_at_pos(self, force, pos, space: int = _abi.SPACE_ENV, hold: int = 1):
+        """gym.apply_rigid_body_force_at_pos_tensors: forces applied at the points `pos` (adds
+        (pos - com) x force to the torque, the body's CoM at the time of the call)."""
+        _check(self.lib.he_apply_body_forces_at_pos(self.h, self._body_rows(force, "force"), self._body_rows(pos, "pos"),
+                                                    int(space), int(hold), self.stream))
+
+    def clear_body_forces(self):
+        """Drop the pending wrench: the next launch runs without one."""
+        _check(self.lib.he_apply_body_forces(self.h, None, None, _abi.SPACE_ENV, 1, self.stream))
 
     # ------------------------------------------------------------------ motion library
     def load_motions(self, tables):

@@ -117,6 +117,15 @@ class EnvConfig:  # config.py:89-157
     # sweeps, so an explicit count other than 4 under TGS warns (resolved_solver_iterations).
     solver_type: int = 1
     solver_iterations: Optional[int] = None
+    # push perturbations (off by default): every push_interval policy steps each env draws a horizontal
+    # direction and a magnitude U(0, push_force) N, applied at push_body's centre of mass through the
+    # next push_duration policy steps (Engine.apply_body_forces); off in test / eval mode unless
+    # push_in_eval
+    push_interval: int = 0
+    push_duration: int = 2
+    push_force: float = 0.0
+    push_body: str = "Torso"
+    push_in_eval: bool = False
 
     def resolved_solver_iterations(self) -> int:
         if self.solver_iterations is None:
@@ -225,6 +234,11 @@ class HumanoidPHC:
         self.flag_im_eval = False
         self._eval_recorder = None
         self._gen = torch.Generator(device=dev).manual_seed(cfg.seed)
+        if cfg.push_body not in BODY_NAMES:
+            raise ValueError(f"push_body {cfg.push_body!r} is not a body of the humanoid")
+        self._push_step = 0   # policy steps taken, counted on the host
+        self._push_left = 0   # policy steps the current push still lasts
+        self._push_f = None   # [N,24,3] the current push (world axes)
         self._term_dist = float(cfg.termination_distance)
         self._reset_bodies = list(range(self.num_bodies))
         self._reset_bodies_backup = list(self._reset_bodies)
@@ -259,6 +273,29 @@ class HumanoidPHC:
                 ids = env_ids.to(device=self.device, dtype=torch.long)
                 self.obs_buf[ids] += torch.randn((len(ids), self.obs_buf.shape[1]), device=self.device,
                                                  generator=self._noise_gen) * self.cfg.obs_noise_std
+
+    def _push(self):
+        """The push option (EnvConfig.push_*), at the start of a policy step: no device read-back."""
+        import torch
+        c = self.cfg
+        t = self._push_step
+        self._push_step += 1
+        if c.push_interval <= 0 or c.push_force <= 0.0 or (self.flag_test and not c.push_in_eval):
+            return
+        if t > 0 and t % c.push_interval == 0:
+            if not hasattr(self, "_push_gen"):  # its own stream: the reset phases stay the same
+                self._push_gen = torch.Generator(device=self.device).manual_seed(c.seed + 104729)
+            u = torch.rand(c.num_envs, 2, device=self.device, generator=self._push_gen)
+            ang, mag = u[:, 0] * (2.0 * np.pi), u[:, 1] * c.push_force
+            if self._push_f is None:
+                self._push_f = torch.zeros(c.num_envs, self.num_bodies, 3, device=self.device)
+            b = BODY_NAMES.index(c.push_body)
+            self._push_f[:, b, 0] = mag * torch.cos(ang)
+            self._push_f[:, b, 1] = mag * torch.sin(ang)
+            self._push_left = c.push_duration
+        if self._push_left > 0:
+            self._push_left -= 1
+            self.engine.apply_body_forces(force=self._push_f, hold=2)  # the policy step's two simulate() calls
 
     def _update_params(self):
         r = dataclasses.asdict(self.cfg.reward)
@@ -314,6 +351,7 @@ class HumanoidPHC:
         return self.obs_buf
 
     def step(self, actions):
+        self._push()
         self.engine.step_actions(actions, 2)
         self._attach_eval()
         self.engine.imitation_step(self._params, self._em, self.obs_buf, self.rew_buf, self.reward_raw,
@@ -500,6 +538,7 @@ class PHCPufferEnv:
         else:
             self.actions[:] = actions.clamp(-1, 1) if self.cfg.clip_actions else actions
         e = self.env
+        e._push()
         e._attach_eval()
         # physics + reward / reset / observation: one launch up to 2048 envs (he_set_fused_step auto),
         # two above, or with eval recording attached; bit-identical either way

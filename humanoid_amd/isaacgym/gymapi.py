@@ -39,6 +39,9 @@ DOF_MODE_POS = 1
 DOF_MODE_VEL = 2
 DOF_MODE_EFFORT = 3
 STATE_NONE, STATE_POS, STATE_VEL, STATE_ALL = 0, 1, 2, 3
+# gymapi.CoordinateSpace (apply_rigid_body_force_tensors, render_env.py:105-126): the envs share one
+# world frame here, so ENV_SPACE and GLOBAL_SPACE are the same frame
+ENV_SPACE, LOCAL_SPACE, GLOBAL_SPACE = _abi.SPACE_ENV, _abi.SPACE_LOCAL, _abi.SPACE_GLOBAL
 
 DofPropertiesDtype = np.dtype([("hasLimits", "?"), ("lower", "<f4"), ("upper", "<f4"), ("driveMode", "<i4"),
                                ("velocity", "<f4"), ("effort", "<f4"), ("stiffness", "<f4"), ("damping", "<f4"),
@@ -399,6 +402,24 @@ class Gym:
     def set_dof_position_target_tensor_indexed(self, sim: Sim, desc, ids_desc, n: int):
         self._flush(sim)
         sim.engine.set_dof_targets_indexed(self._tensor(desc), self._tensor(ids_desc)[:n])
+        return True
+
+    # -- external forces (render_env.py:105-126) ------------------------------------------------------
+    def apply_rigid_body_force_tensors(self, sim: Sim, force_desc=None, torque_desc=None, space: int = ENV_SPACE):
+        """Forces at the bodies' centres of mass and torques, [N*24,3] each (a None descriptor: absent),
+        acting during the next ``simulate`` only, as Isaac Gym clears them after each simulation step."""
+        self._flush(sim)
+        f = None if force_desc is None else self._tensor(force_desc)
+        t = None if torque_desc is None else self._tensor(torque_desc)
+        if f is None and t is None:
+            return False  # Isaac Gym: nothing to apply (the engine's clear is Engine.clear_body_forces)
+        sim.engine.apply_body_forces(f, t, int(space), hold=1)
+        return True
+
+    def apply_rigid_body_force_at_pos_tensors(self, sim: Sim, force_desc, pos_desc, space: int = ENV_SPACE):
+        """Forces applied at the points ``pos`` ([N*24,3] each), acting during the next ``simulate``."""
+        self._flush(sim)
+        sim.engine.apply_body_forces_at_pos(self._tensor(force_desc), self._tensor(pos_desc), int(space), hold=1)
         return True
 
     # -- stepping -----------------------------------------------------------------------------------

@@ -237,6 +237,32 @@ int he_step_actions(he_engine* h, const float* actions, int num_simulate, void* 
  * as the reference relies on, humanoid_phc.py:922-931). */
 int he_refresh(he_engine* h, void* stream);
 
+/* gym.apply_rigid_body_force_tensors / apply_rigid_body_force_at_pos_tensors (the reference's use:
+ * puffer_phc/envs/render_env.py:105-126, 3500 N shoves on two bodies in ENV_SPACE). External
+ * wrenches on bodies: force / torque (or force / application point) are DEVICE arrays [N*24,3], rows
+ * as HE_BUF_RB_STATE's. In he_apply_body_forces either pointer may be NULL (absent); both NULL
+ * clears what is pending. The force acts at the body's centre of mass; the at-position form adds
+ * (pos - com) x force to the torque, with the body's world CoM at the time of the call.
+ * `space` (gymapi.CoordinateSpace): ENV and GLOBAL are the same frame here (the envs share one world
+ * frame); LOCAL vectors and points are in the body frame and are rotated by the body's current
+ * rigid-body rotation at the call, then stay fixed in the world. Calls made before the next physics
+ * launch accumulate. A pending wrench acts during the next `hold` gym.simulate() calls (hold
+ * x he_sim_params.substeps physics steps, across he_simulate / he_step_actions / he_env_step
+ * launches; the rest of a longer launch runs without it), then is gone: hold = 1 is Isaac Gym's
+ * rule (forces are cleared after each simulation step), hold > 1 the engine's extension for pushes
+ * that last whole policy steps. A later call replaces the remaining hold by its own. A reset does
+ * not clear an env's pending wrench; mass_scale does not scale it; HE_BUF_DOF_FORCE and
+ * HE_BUF_CONTACT_FORCE report the drives and the contacts as without it. Nonzero (reason in
+ * he_last_error) for a null handle, no envs, a space outside 0..2, hold < 1, or the at-position
+ * form with only one of its two pointers. */
+#define HE_SPACE_ENV 0
+#define HE_SPACE_LOCAL 1
+#define HE_SPACE_GLOBAL 2
+int he_apply_body_forces(he_engine* h, const float* force, const float* torque, int space, int hold,
+                         void* stream);
+int he_apply_body_forces_at_pos(he_engine* h, const float* force, const float* pos, int space, int hold,
+                                void* stream);
+
 /* ---------------- motion library + fused imitation kernel (A5-A9) ---------------------- */
 /* MotionLibBase.load_motions table upload (motion_lib.py:396-420). Host pointers; the engine
  * re-lays the frames out as interleaved per-frame records in device memory.
