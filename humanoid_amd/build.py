@@ -1,4 +1,5 @@
-"""Build ``humanoid_amd/libhumanoid_engine.so`` for gfx950 with hipcc (in-tree, travels with the
+"""Build ``humanoid_amd/libhumanoid_engine.so`` (with its diagnostic twin) and the camera-sensor
+library ``humanoid_amd/libhumanoid_render.so`` for gfx950 with hipcc (in-tree, they travel with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
 import hashlib
 import os
@@ -13,6 +14,10 @@ LIB = os.path.join(HERE, "libhumanoid_engine.so")
 # the product library leaves them out (their per-phase branches cost ~1% of the step)
 PHASES_LIB = os.path.join(HERE, "libhumanoid_engine_phases.so")
 PHASES_DEFS = {"he_physics.hip": ["-DHE_PHASE_STAMPS=1"]}
+# the camera-sensor ray caster (include/humanoid_render.h): a library of its own that only reads the
+# engine's buffers, so the engine's device code (device_code_id) does not move with it
+RENDER_LIB = os.path.join(HERE, "libhumanoid_render.so")
+RENDER_SOURCES = [("hr_render.hip", [])]
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("HE_OFFLOAD_ARCH", "gfx950")
 
@@ -32,7 +37,8 @@ SOURCES = [
     ("he_engine.cpp", ["-x", "hip"]),
 ]
 HEADERS = ["he_kernels.h", "he_math.h", "he_imitation_env.h", "he_topo.h", "he_regla.h", "he_smpl_topo.h", os.path.join("..", "..", "include", "humanoid_engine.h"),
-           os.path.join("..", "..", "include", "humanoid_rollout.h")]
+           os.path.join("..", "..", "include", "humanoid_rollout.h"),
+           os.path.join("..", "..", "include", "humanoid_render.h")]
 
 
 def _hipcc():
@@ -52,6 +58,27 @@ MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2)}
 # how many kernels of the TU match the watched name (physics_kernel and physics_kernel_tgs): a report
 # that lists fewer fails the build, so neither can drop out of the check unnoticed
 MIN_KERNELS = {"he_physics.hip": 2}
+# kernels that must not touch scratch memory (no spilled registers, no stack): the render kernel keeps
+# its primitives in LDS and everything else in registers
+NO_SCRATCH = {"hr_render.hip": "render_kernel"}
+
+
+def _check_scratch(src, stderr):
+    name = NO_SCRATCH.get(os.path.basename(src))
+    if not name:
+        return
+    lines = stderr.splitlines()
+    for i, ln in enumerate(lines):
+        if "Function Name:" in ln and name in ln:
+            for ln2 in lines[i + 1:]:
+                if "Function Name:" in ln2:
+                    break
+                m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln2)
+                if m:
+                    if int(m.group(1)) != 0:
+                        raise RuntimeError(f"{name}: {m.group(1)} bytes/lane of scratch (spills or a stack)")
+                    return
+    raise RuntimeError(f"{name}: no scratch size in the compiler's resource report")
 
 
 def _check_occupancy(src, stderr):
@@ -92,7 +119,7 @@ def _compile(hipcc, cmd, src, o, force, hdr_time, verbose):
     if force or not same_cmd or _mtime(o) < max(_mtime(src), hdr_time):
         if verbose:
             print(" ".join(cmd))
-        if os.path.basename(src) in MIN_OCCUPANCY:
+        if os.path.basename(src) in MIN_OCCUPANCY or os.path.basename(src) in NO_SCRATCH:
             cmd = cmd + ["-Rpass-analysis=kernel-resource-usage"]
         # a failed compile or occupancy check leaves neither the object nor the stamp behind, so the
         # next build cannot mistake a rejected object for an up-to-date one
@@ -103,6 +130,7 @@ def _compile(hipcc, cmd, src, o, force, hdr_time, verbose):
             raise RuntimeError(f"hipcc failed for {os.path.basename(src)}:\n{r.stderr}")
         try:
             _check_occupancy(src, r.stderr)
+            _check_scratch(src, r.stderr)
         except RuntimeError:
             _discard(o, stamp)
             raise
@@ -145,6 +173,14 @@ def build(force=False, verbose=False):
             cmd = [hipcc] + common + [cuid] + flags + defs.get(src, []) + ["-c", s, "-o", o]
             _compile(hipcc, cmd, s, o, force and lib == LIB or force and src in defs, hdr_time, verbose)
         _link(hipcc, lib, objs, force)
+    objs = []
+    for src, flags in RENDER_SOURCES:
+        s = os.path.join(CSRC, src)
+        o = os.path.join(BUILD, src + ".o")
+        objs.append(o)
+        cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
+        _compile(hipcc, [hipcc] + common + [cuid] + flags + ["-c", s, "-o", o], s, o, force, hdr_time, verbose)
+    _link(hipcc, RENDER_LIB, objs, force)
     return LIB
 
 

@@ -1,0 +1,555 @@
+// libhumanoid_render.so: the camera-sensor ray caster (include/humanoid_render.h defines the image).
+// One launch draws every camera: grid (ceil(W/16), ceil(H/16), K), 256 threads, one pixel per thread.
+//   prologue   lanes 0..47 of wave 0 put the env's primitives (24 body geoms, then the markers) into
+//              LDS in world space, lane 48 the camera (resolved from its body when it follows one);
+//   culling    each wave (a 16 x 4 pixel strip) tests its rays against every primitive's bounding
+//              sphere and keeps the primitives any lane may hit as a 64-bit wave-uniform mask; the
+//              pixel loop walks the set bits, so the trip count is the same in all lanes and only the
+//              hit tests diverge. The shadow rays get a second mask over the 24 bodies;
+//   stores     masked (partial tiles run every barrier), one packed 32-bit colour store per pixel.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/humanoid_render.h"
+
+namespace {
+
+constexpr int NB = HE_NUM_BODIES;
+constexpr int kMaxPrims = NB + HR_MAX_MARKERS;  // 48: one bit each of the wave's 64-bit mask
+constexpr int kTile = 16;
+constexpr int kGeomWords = 11;  // per body on the device: geom_type bits, geom_params[10]
+
+// device copy of a camera (hr_set_cameras): the tangent of the half fov is taken on the host
+struct DCam {
+    int32_t env, follow_body, follow_mode;
+    float th, nearp, farp;
+    float pos[3], target[3];
+};
+
+struct Params {
+    const float* rb;        // [N*24,13]
+    const float* geom;      // [24][kGeomWords]
+    const DCam* cams;       // [K]
+    const float* body_rgb;  // [N,24,3] or null
+    const int32_t* body_seg;  // [N,24] or null
+    const float* mpos;      // [N,m,3]
+    const float* mrgb;      // [m,3]
+    uint32_t* color;        // [K,H,W] packed RGBA8, or null
+    float* depth;           // [K,H,W] or null
+    int32_t* seg;           // [K,H,W] or null
+    int32_t W, H, m;
+    uint32_t flags;
+    float mradius;
+};
+
+struct f3 {
+    float x, y, z;
+};
+__device__ inline f3 operator+(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ inline f3 operator-(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ inline f3 operator*(f3 a, float s) { return f3{a.x * s, a.y * s, a.z * s}; }
+__device__ inline float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ inline f3 cross(f3 a, f3 b) { return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ inline f3 normalize(f3 a) { return a * (1.f / sqrtf(dot(a, a))); }
+__device__ inline f3 ld3(const float* p) { return f3{p[0], p[1], p[2]}; }
+
+// rot(q, v) = (v + w t) + qv x t, t = 2 (qv x v)
+__device__ inline f3 rot(const float* q, f3 v) {
+    const f3 qv{q[0], q[1], q[2]};
+    const f3 t = cross(qv, v) * 2.f;
+    return (v + t * q[3]) + cross(qv, t);
+}
+
+// The following camera's world points, each product and sum rounded on its own (the header's promise
+// that a fixed camera at host-computed points draws the same bits): no contraction in here.
+__device__ inline void camera_points(const DCam& c, const float* rb, f3& P, f3& T) {
+#pragma clang fp contract(off)
+    P = ld3(c.pos);
+    T = ld3(c.target);
+    if (c.follow_body >= 0) {
+        const float* row = rb + ((size_t)c.env * NB + c.follow_body) * 13;
+        const f3 p = ld3(row);
+        if (c.follow_mode == HR_FOLLOW_TRANSFORM) {
+            const float qx = row[3], qy = row[4], qz = row[5], qw = row[6];
+            f3 v[2] = {P, T};
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const f3 a = v[i];
+                const float tx = 2.f * (qy * a.z - qz * a.y);
+                const float ty = 2.f * (qz * a.x - qx * a.z);
+                const float tz = 2.f * (qx * a.y - qy * a.x);
+                const float cx = qy * tz - qz * ty;
+                const float cy = qz * tx - qx * tz;
+                const float cz = qx * ty - qy * tx;
+                v[i] = f3{(a.x + qw * tx) + cx, (a.y + qw * ty) + cy, (a.z + qw * tz) + cz};
+            }
+            P = v[0];
+            T = v[1];
+        }
+        const bool xy = c.follow_mode == HR_FOLLOW_POSITION_XY;  // the heights stay absolute
+        P = f3{p.x + P.x, p.y + P.y, xy ? P.z : p.z + P.z};
+        T = f3{p.x + T.x, p.y + T.y, xy ? T.z : p.z + T.z};
+    }
+}
+
+// a primitive in LDS (24 words)
+struct Prim {
+    int32_t type;  // HE_GEOM_*
+    float bc[3];   // bounding sphere
+    float br;
+    float g[15];   // sphere: C3 r | capsule: A3 w3 L r B3 | box: C3 e3 R9 (columns)
+    float rgb[3];
+    int32_t seg;
+};
+struct Cam {
+    float o[3], f[3], r[3], u[3];
+    float tx, ty, nearp, farp;
+};
+
+// entry hit of a sphere, m = o - C
+__device__ inline bool hit_sphere(f3 m, f3 d, float r, float& t, f3& n) {
+    const float b = dot(m, d);
+    const f3 q = m - d * b;
+    const float h = r * r - dot(q, q);
+    if (h < 0.f) return false;
+    t = -b - sqrtf(h);
+    n = (m + d * t) * (1.f / r);
+    return true;
+}
+
+__device__ inline bool intersect(const Prim& p, f3 o, f3 d, float& t, f3& n) {
+    const float* g = p.g;
+    const int type = p.type;
+    if (type == HE_GEOM_SPHERE) return hit_sphere(o - ld3(g), d, g[3], t, n);
+    if (type == HE_GEOM_CAPSULE) {
+        const f3 m = o - ld3(g), w = ld3(g + 3);
+        const float L = g[6], r = g[7];
+        bool hit = hit_sphere(m, d, r, t, n);
+        float t2;
+        f3 n2;
+        if (hit_sphere(o - ld3(g + 8), d, r, t2, n2) && (!hit || t2 < t)) {
+            t = t2;
+            n = n2;
+            hit = true;
+        }
+        const float mw = dot(m, w), dw = dot(d, w);
+        const f3 mp = m - w * mw, dp = d - w * dw;
+        const float a = dot(dp, dp);
+        const f3 c = cross(mp, dp);
+        const float h = a * r * r - dot(c, c);
+        if (a >= 1e-12f && h >= 0.f) {
+            t2 = (-dot(mp, dp) - sqrtf(h)) / a;
+            const float s = mw + t2 * dw;
+            if (s >= 0.f && s <= L && (!hit || t2 < t)) {
+                t = t2;
+                n = (mp + dp * t2) * (1.f / r);
+                hit = true;
+            }
+        }
+        return hit;
+    }
+    // box: slabs in the box frame
+    const f3 mo = o - ld3(g);
+    const f3 c0 = ld3(g + 6), c1 = ld3(g + 9), c2 = ld3(g + 12);
+    const float ol[3] = {dot(c0, mo), dot(c1, mo), dot(c2, mo)};
+    const float dl[3] = {dot(c0, d), dot(c1, d), dot(c2, d)};
+    float lo[3], tn = -INFINITY, tf = INFINITY;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float t1 = (-g[3 + k] - ol[k]) / dl[k], t2 = (g[3 + k] - ol[k]) / dl[k];
+        lo[k] = fminf(t1, t2);
+        tn = fmaxf(tn, lo[k]);
+        tf = fminf(tf, fmaxf(t1, t2));
+    }
+    if (!(tn <= tf)) return false;
+    t = tn;
+    const int k = lo[0] == tn ? 0 : (lo[1] == tn ? 1 : 2);
+    const f3 ax = k == 0 ? c0 : (k == 1 ? c1 : c2);
+    const float dk = k == 0 ? dl[0] : (k == 1 ? dl[1] : dl[2]);
+    n = ax * (dk > 0.f ? -1.f : 1.f);
+    return true;
+}
+
+// may the ray touch the primitive's bounding sphere? Conservative: the slack covers the rounding of
+// the test itself (|q| carries about 4e-7 |m|), so culling never changes a pixel.
+__device__ inline bool may_hit(const Prim& p, f3 o, f3 d) {
+    const f3 m = o - ld3(p.bc);
+    const float b = dot(m, d), mm = dot(m, m);
+    const f3 q = m - d * b;
+    const float slack = 1e-5f * mm + 1e-4f;
+    return dot(q, q) <= p.br * p.br + slack && b <= p.br + slack;
+}
+
+__device__ void build_prim(const Params& P, int env, int i, Prim& out) {
+    if (i < NB) {
+        const float* row = P.rb + ((size_t)env * NB + i) * 13;
+        const float* q = row + 3;
+        const f3 p = ld3(row);
+        const float* g = P.geom + i * kGeomWords;
+        const int type = __float_as_int(g[0]);
+        const float* gp = g + 1;
+        out.type = type;
+        f3 bc;
+        float br;
+        if (type == HE_GEOM_SPHERE) {
+            bc = p + rot(q, ld3(gp));
+            br = gp[3];
+            out.g[0] = bc.x, out.g[1] = bc.y, out.g[2] = bc.z, out.g[3] = gp[3];
+        } else if (type == HE_GEOM_CAPSULE) {
+            const f3 A = p + rot(q, ld3(gp)), B = p + rot(q, ld3(gp + 3));
+            const f3 ab = B - A;
+            float L = sqrtf(dot(ab, ab));
+            f3 w{0.f, 0.f, 1.f};
+            if (L < 1e-9f) L = 0.f;
+            else w = ab * (1.f / L);
+            out.g[0] = A.x, out.g[1] = A.y, out.g[2] = A.z;
+            out.g[3] = w.x, out.g[4] = w.y, out.g[5] = w.z;
+            out.g[6] = L, out.g[7] = gp[6];
+            out.g[8] = B.x, out.g[9] = B.y, out.g[10] = B.z;
+            bc = (A + B) * 0.5f;
+            br = 0.5f * L + gp[6];
+        } else {
+            bc = p + rot(q, ld3(gp));
+            // Hamilton product q * qb
+            const float ax = q[0], ay = q[1], az = q[2], aw = q[3];
+            const float bx = gp[6], by = gp[7], bz = gp[8], bw = gp[9];
+            const float x = aw * bx + ax * bw + ay * bz - az * by;
+            const float y = aw * by - ax * bz + ay * bw + az * bx;
+            const float z = aw * bz + ax * by - ay * bx + az * bw;
+            const float w = aw * bw - ax * bx - ay * by - az * bz;
+            out.g[0] = bc.x, out.g[1] = bc.y, out.g[2] = bc.z;
+            out.g[3] = gp[3], out.g[4] = gp[4], out.g[5] = gp[5];
+            out.g[6] = 1.f - 2.f * (y * y + z * z), out.g[7] = 2.f * (x * y + w * z), out.g[8] = 2.f * (x * z - w * y);
+            out.g[9] = 2.f * (x * y - w * z), out.g[10] = 1.f - 2.f * (x * x + z * z), out.g[11] = 2.f * (y * z + w * x);
+            out.g[12] = 2.f * (x * z + w * y), out.g[13] = 2.f * (y * z - w * x), out.g[14] = 1.f - 2.f * (x * x + y * y);
+            br = sqrtf(gp[3] * gp[3] + gp[4] * gp[4] + gp[5] * gp[5]);
+        }
+        out.bc[0] = bc.x, out.bc[1] = bc.y, out.bc[2] = bc.z;
+        out.br = br * 1.001f + 1e-4f;
+        const size_t a = (size_t)env * NB + i;
+        out.rgb[0] = P.body_rgb ? P.body_rgb[a * 3 + 0] : HR_BODY_R;
+        out.rgb[1] = P.body_rgb ? P.body_rgb[a * 3 + 1] : HR_BODY_G;
+        out.rgb[2] = P.body_rgb ? P.body_rgb[a * 3 + 2] : HR_BODY_B;
+        out.seg = P.body_seg ? P.body_seg[a] : 0;
+    } else {
+        const int k = i - NB;
+        const float* c = P.mpos + ((size_t)env * P.m + k) * 3;
+        out.type = HE_GEOM_SPHERE;
+        out.g[0] = out.bc[0] = c[0], out.g[1] = out.bc[1] = c[1], out.g[2] = out.bc[2] = c[2];
+        out.g[3] = P.mradius;
+        out.br = P.mradius * 1.001f + 1e-4f;
+        out.rgb[0] = P.mrgb[k * 3], out.rgb[1] = P.mrgb[k * 3 + 1], out.rgb[2] = P.mrgb[k * 3 + 2];
+        out.seg = HR_SEG_MARKER;
+    }
+}
+
+__device__ void build_camera(const Params& P, const DCam& c, Cam& out) {
+    f3 o, T;
+    camera_points(c, P.rb, o, T);
+    const f3 f = normalize(T - o);
+    f3 r = cross(f, f3{0.f, 0.f, 1.f});
+    if (dot(r, r) < 1e-12f) r = cross(f, f3{0.f, 1.f, 0.f});  // |f x z| < 1e-6
+    r = normalize(r);
+    const f3 u = cross(r, f);
+    out.o[0] = o.x, out.o[1] = o.y, out.o[2] = o.z;
+    out.f[0] = f.x, out.f[1] = f.y, out.f[2] = f.z;
+    out.r[0] = r.x, out.r[1] = r.y, out.r[2] = r.z;
+    out.u[0] = u.x, out.u[1] = u.y, out.u[2] = u.z;
+    out.tx = c.th;
+    out.ty = c.th * (float)P.H / (float)P.W;
+    out.nearp = c.nearp;
+    out.farp = c.farp;
+}
+
+__device__ inline uint32_t channel(float c) {
+    c = fminf(fmaxf(c, 0.f), 1.f);
+    return (uint32_t)(int)(c * 255.f + 0.5f);
+}
+
+__global__ __launch_bounds__(256) void render_kernel(const Params P) {
+    __shared__ Prim prims[kMaxPrims];
+    __shared__ Cam cam;
+    const int tid = threadIdx.y * kTile + threadIdx.x;
+    const int k = blockIdx.z;
+    const DCam& dc = P.cams[k];
+    const int env = dc.env;
+    const int nprim = NB + P.m;
+    if (tid < nprim) build_prim(P, env, tid, prims[tid]);
+    if (tid == kMaxPrims) build_camera(P, dc, cam);
+    __syncthreads();  // every thread of the workgroup, partial tiles included
+
+    const int j = blockIdx.x * kTile + threadIdx.x, i = blockIdx.y * kTile + threadIdx.y;
+    const bool valid = j < P.W && i < P.H;
+    const f3 o = ld3(cam.o), f = ld3(cam.f);
+    const float x = (2.f * ((float)j + 0.5f) / (float)P.W - 1.f) * cam.tx;
+    const float y = (1.f - 2.f * ((float)i + 0.5f) / (float)P.H) * cam.ty;
+    const f3 d = normalize(f + ld3(cam.r) * x + ld3(cam.u) * y);
+    const float nearp = cam.nearp, farp = cam.farp;
+
+    // the primitives any ray of this wave may hit
+    const bool cull = !(P.flags & HR_FLAG_NO_CULL);
+    unsigned long long mask = nprim >= 64 ? ~0ull : ((1ull << nprim) - 1ull);
+    if (cull) {
+        mask = 0ull;
+        for (int p = 0; p < nprim; ++p)
+            if (__ballot(valid && may_hit(prims[p], o, d)) != 0ull) mask |= 1ull << p;
+    }
+
+    float best = INFINITY;
+    int who = -2;  // -2 sky, -1 ground, else the primitive
+    f3 n{0.f, 0.f, 1.f};
+    if (d.z < 0.f && o.z > 0.f) {
+        const float t = -o.z / d.z;
+        if (t >= nearp && t <= farp) {
+            best = t;
+            who = -1;
+        }
+    }
+    for (unsigned long long mm = mask; mm != 0ull; mm &= mm - 1ull) {
+        const int p = __builtin_ctzll(mm);
+        float t;
+        f3 nn;
+        if (intersect(prims[p], o, d, t, nn) && t >= nearp && t <= farp && t < best) {
+            best = t;
+            who = p;
+            n = nn;
+        }
+    }
+
+    float cr = HR_SKY_R, cg = HR_SKY_G, cb = HR_SKY_B;
+    int sid = 0;
+    const bool hit = who > -2;
+    const f3 hp = o + d * best;
+    const f3 l{HR_LIGHT_X, HR_LIGHT_Y, HR_LIGHT_Z};
+    const float ndl = fmaxf(0.f, dot(n, l));
+    // shadow rays: a second wave-uniform mask over the body geoms
+    float s = 1.f;
+    if (P.flags & HR_FLAG_SHADOWS) {
+        const bool want = valid && hit && ndl > 0.f;
+        const f3 so = hp + n * HR_SHADOW_EPS;
+        unsigned long long smask = 0ull;
+        if (cull) {
+            for (int p = 0; p < NB; ++p)
+                if (__ballot(want && may_hit(prims[p], so, l)) != 0ull) smask |= 1ull << p;
+        } else if (__ballot(want) != 0ull) {
+            smask = (1ull << NB) - 1ull;
+        }
+        for (unsigned long long mm = smask; mm != 0ull; mm &= mm - 1ull) {
+            const int p = __builtin_ctzll(mm);
+            float t;
+            f3 nn;
+            if (want && intersect(prims[p], so, l, t, nn) && t >= 0.f) s = HR_SHADOW;
+        }
+    }
+    if (hit) {
+        float ar, ag, ab;
+        if (who < 0) {
+            const int par = (int)floorf(hp.x) + (int)floorf(hp.y);
+            ar = ag = ab = ((P.flags & HR_FLAG_CHECKER) && (par & 1)) ? HR_GROUND_ODD : HR_GROUND_EVEN;
+        } else {
+            ar = prims[who].rgb[0], ag = prims[who].rgb[1], ab = prims[who].rgb[2];
+            sid = prims[who].seg;
+        }
+        const float shade = HR_AMBIENT + (1.f - HR_AMBIENT) * ndl * s;
+        cr = ar * shade, cg = ag * shade, cb = ab * shade;
+    }
+    if (valid) {
+        const size_t px = ((size_t)k * P.H + i) * P.W + j;
+        if (P.color) P.color[px] = channel(cr) | channel(cg) << 8 | channel(cb) << 16 | 0xff000000u;
+        if (P.depth) P.depth[px] = hit ? -best * dot(d, f) : -INFINITY;
+        if (P.seg) P.seg[px] = sid;
+    }
+}
+
+thread_local std::string g_err;
+
+int fail(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return 1;
+}
+
+#define HR_CHECK(expr)                                                                   \
+    do {                                                                                 \
+        hipError_t _e = (expr);                                                          \
+        if (_e != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(_e));       \
+    } while (0)
+
+}  // namespace
+
+struct hr_renderer {
+    int device = 0;
+    int num_envs = 0;
+    float* d_geom = nullptr;
+    float* d_mrgb = nullptr;  // [HR_MAX_MARKERS,3]
+    DCam* d_cams = nullptr;
+    int cam_cap = 0;
+    int k = 0, W = 0, H = 0;
+    const float* body_rgb = nullptr;
+    const int32_t* body_seg = nullptr;
+    const float* mpos = nullptr;
+    int m = 0;
+    float mradius = 0.f;
+};
+
+extern "C" {
+
+const char* hr_last_error(void) { return g_err.c_str(); }
+int hr_version(void) { return 1; }
+
+int hr_create(int device, const he_model* model, int num_envs, hr_renderer** out) {
+    if (!out) return fail("hr_create: null output pointer");
+    *out = nullptr;
+    if (!model) return fail("hr_create: null model");
+    if (num_envs < 1) return fail("hr_create: num_envs %d < 1", num_envs);
+    if (model->num_bodies != NB) return fail("hr_create: the renderer draws %d bodies, the model has %d", NB, model->num_bodies);
+    float geom[NB * kGeomWords];
+    for (int b = 0; b < NB; ++b) {
+        const int32_t t = model->geom_type[b];
+        if (t != HE_GEOM_SPHERE && t != HE_GEOM_CAPSULE && t != HE_GEOM_BOX)
+            return fail("hr_create: body %d has geom type %d", b, t);
+        memcpy(&geom[b * kGeomWords], &t, sizeof(t));
+        memcpy(&geom[b * kGeomWords + 1], model->geom_params[b], 10 * sizeof(float));
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail("hr_create: no HIP device visible (the renderer has no CPU path)");
+    if (device < 0 || device >= count) return fail("hr_create: device %d of %d", device, count);
+    HR_CHECK(hipSetDevice(device));
+    hr_renderer* h = new hr_renderer;
+    h->device = device;
+    h->num_envs = num_envs;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_geom), sizeof(geom));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_mrgb), HR_MAX_MARKERS * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_geom, geom, sizeof(geom), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hr_destroy(h);
+        return fail("hr_create: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return 0;
+}
+
+int hr_destroy(hr_renderer* h) {
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    if (h->d_geom) (void)hipFree(h->d_geom);
+    if (h->d_mrgb) (void)hipFree(h->d_mrgb);
+    if (h->d_cams) (void)hipFree(h->d_cams);
+    delete h;
+    return 0;
+}
+
+int hr_validate_cameras(const hr_camera* c, int k, int num_envs) {
+    if (k < 1) return fail("camera set: k = %d < 1", k);
+    if (!c) return fail("camera set: null camera array");
+    for (int i = 0; i < k; ++i) {
+        if (c[i].width < 1 || c[i].height < 1) return fail("camera %d: size %d x %d is not positive", i, c[i].width, c[i].height);
+        if (c[i].width != c[0].width || c[i].height != c[0].height)
+            return fail("camera %d is %d x %d, camera 0 is %d x %d: the cameras of one renderer share one size", i,
+                        c[i].width, c[i].height, c[0].width, c[0].height);
+        if (!(c[i].hfov_deg > 0.f && c[i].hfov_deg < 180.f)) return fail("camera %d: horizontal fov %g not in (0, 180)", i, c[i].hfov_deg);
+        if (!(c[i].near > 0.f)) return fail("camera %d: near plane %g is not positive", i, c[i].near);
+        if (!(c[i].far >= c[i].near)) return fail("camera %d: far plane %g before the near plane %g", i, c[i].far, c[i].near);
+        if (c[i].env < 0 || c[i].env >= num_envs) return fail("camera %d: env %d outside [0, %d)", i, c[i].env, num_envs);
+        if (c[i].follow_body < -1 || c[i].follow_body >= NB) return fail("camera %d: follow_body %d outside [-1, %d)", i, c[i].follow_body, NB);
+        if (c[i].follow_mode < HR_FOLLOW_POSITION || c[i].follow_mode > HR_FOLLOW_POSITION_XY)
+            return fail("camera %d: follow_mode %d is not 0 (position), 1 (transform) or 2 (position xy)", i, c[i].follow_mode);
+    }
+    return 0;
+}
+
+int hr_set_cameras(hr_renderer* h, const hr_camera* c, int k) {
+    if (!h) return fail("hr_set_cameras: null handle");
+    if (hr_validate_cameras(c, k, h->num_envs)) return 1;
+    if ((long long)k > 65535) return fail("hr_set_cameras: %d cameras, at most 65535 in one launch", k);
+    std::vector<DCam> dc(k);
+    for (int i = 0; i < k; ++i) {
+        dc[i].env = c[i].env;
+        dc[i].follow_body = c[i].follow_body;
+        dc[i].follow_mode = c[i].follow_mode;
+        dc[i].th = (float)tan((double)c[i].hfov_deg * (M_PI / 360.0));
+        dc[i].nearp = c[i].near;
+        dc[i].farp = c[i].far;
+        for (int a = 0; a < 3; ++a) dc[i].pos[a] = c[i].pos[a], dc[i].target[a] = c[i].target[a];
+    }
+    HR_CHECK(hipSetDevice(h->device));
+    if (k > h->cam_cap) {
+        DCam* p = nullptr;
+        HR_CHECK(hipMalloc(reinterpret_cast<void**>(&p), k * sizeof(DCam)));
+        if (h->d_cams) (void)hipFree(h->d_cams);
+        h->d_cams = p;
+        h->cam_cap = k;
+    }
+    HR_CHECK(hipMemcpy(h->d_cams, dc.data(), k * sizeof(DCam), hipMemcpyHostToDevice));
+    h->k = k;
+    h->W = c[0].width;
+    h->H = c[0].height;
+    return 0;
+}
+
+int hr_set_appearance(hr_renderer* h, const float* body_rgb, const int32_t* body_seg) {
+    if (!h) return fail("hr_set_appearance: null handle");
+    h->body_rgb = body_rgb;
+    h->body_seg = body_seg;
+    return 0;
+}
+
+int hr_set_markers(hr_renderer* h, const float* pos, int m, const float* host_rgb, float radius) {
+    if (!h) return fail("hr_set_markers: null handle");
+    if (m < 0 || m > HR_MAX_MARKERS) return fail("hr_set_markers: %d markers, 0..%d per env", m, HR_MAX_MARKERS);
+    if (m == 0) {
+        h->m = 0;
+        h->mpos = nullptr;
+        return 0;
+    }
+    if (!pos || !host_rgb) return fail("hr_set_markers: null positions or colours");
+    if (!(radius > 0.f)) return fail("hr_set_markers: radius %g is not positive", radius);
+    HR_CHECK(hipSetDevice(h->device));
+    HR_CHECK(hipMemcpy(h->d_mrgb, host_rgb, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
+    h->mpos = pos;
+    h->m = m;
+    h->mradius = radius;
+    return 0;
+}
+
+int hr_render(hr_renderer* h, const float* rb_state, uint8_t* color, float* depth, int32_t* seg, uint32_t flags,
+              void* stream) {
+    if (!h) return fail("hr_render: null handle");
+    if (h->k < 1) return fail("hr_render: no cameras (hr_set_cameras)");
+    if (!rb_state) return fail("hr_render: null rb_state");
+    if (!color && !depth && !seg) return fail("hr_render: no output buffer");
+    if (reinterpret_cast<uintptr_t>(color) & 3u) return fail("hr_render: the colour buffer must be 4-byte aligned");
+    Params P{};
+    P.rb = rb_state;
+    P.geom = h->d_geom;
+    P.cams = h->d_cams;
+    P.body_rgb = h->body_rgb;
+    P.body_seg = h->body_seg;
+    P.mpos = h->mpos;
+    P.mrgb = h->d_mrgb;
+    P.color = reinterpret_cast<uint32_t*>(color);
+    P.depth = depth;
+    P.seg = seg;
+    P.W = h->W;
+    P.H = h->H;
+    P.m = h->m;
+    P.flags = flags;
+    P.mradius = h->mradius;
+    const dim3 grid((h->W + kTile - 1) / kTile, (h->H + kTile - 1) / kTile, h->k);
+    if (grid.y > 65535u) return fail("hr_render: image height %d too large for one launch", h->H);
+    hipLaunchKernelGGL(render_kernel, grid, dim3(kTile, kTile, 1), 0, static_cast<hipStream_t>(stream), P);
+    HR_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

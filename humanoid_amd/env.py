@@ -126,6 +126,11 @@ class EnvConfig:  # config.py:89-157
     push_force: float = 0.0
     push_body: str = "Torso"
     push_in_eval: bool = False
+    # camera sensor (off by default): render() returns the RGBA frame of env `viewing_env_idx`, drawn by
+    # the HIP ray caster (humanoid_amd/render.py) with the reference motion as red marker spheres
+    camera: bool = False
+    camera_width: int = 640
+    camera_height: int = 360
 
     def resolved_solver_iterations(self) -> int:
         if self.solver_iterations is None:
@@ -233,6 +238,7 @@ class HumanoidPHC:
         self.flag_test = False
         self.flag_im_eval = False
         self._eval_recorder = None
+        self.viewing_env_idx = 0  # the env render() shows (render_env.py:221)
         self._gen = torch.Generator(device=dev).manual_seed(cfg.seed)
         if cfg.push_body not in BODY_NAMES:
             raise ValueError(f"push_body {cfg.push_body!r} is not a body of the humanoid")
@@ -463,10 +469,48 @@ class HumanoidPHC:
     def _contact_forces(self):
         return self.engine.contact_forces.view(self.cfg.num_envs, self.num_bodies, 3)
 
+    # -- camera sensor (render_env.py:151-171, 375-431) -----------------------------------------
+    # matplotlib's default colour cycle, which render_env.py:30-31 indexes by env (agt_color)
+    PALETTE = ((0.122, 0.467, 0.706), (1.000, 0.498, 0.055), (0.173, 0.627, 0.173), (0.839, 0.153, 0.157),
+               (0.580, 0.404, 0.741), (0.549, 0.337, 0.294), (0.890, 0.467, 0.761), (0.498, 0.498, 0.498),
+               (0.737, 0.741, 0.133), (0.090, 0.745, 0.812))
+
+    def _init_camera(self):
+        import torch
+        from . import render as R
+        n = self.cfg.num_envs
+        self._viewed = None
+        self._renderer = R.Renderer(self.engine)
+        pal = torch.tensor(self.PALETTE, dtype=torch.float32, device=self.device)
+        self._body_rgb = pal[torch.arange(n, device=self.device) % len(self.PALETTE)][:, None, :].expand(
+            n, self.num_bodies, 3).contiguous()
+        self._renderer.set_appearance(self._body_rgb, None)
+        self._marker_pos = torch.zeros(n, self.num_bodies, 3, device=self.device)
+        self._renderer.set_markers(self._marker_pos, (0.8, 0.0, 0.0), radius=0.05)  # traj_marker.urdf, :319-326
+
     def render(self):
-        return None
+        """With ``cfg.camera``: the RGBA frame uint8 [H,W,4] (a device tensor, overwritten by the next call)
+        of env ``viewing_env_idx``; the camera follows that env's root (render_env.py:407-411: target = root
+        xy at z = 1, position = root xy - (0, 4) at z = 2), resolved on the device, and the reference motion
+        of the tracked bodies at (progress + 1) dt is drawn as red markers (:416-431). Otherwise ``None``."""
+        if not self.cfg.camera:
+            return None
+        from . import render as R
+        if getattr(self, "_renderer", None) is None:
+            self._init_camera()
+        if self._viewed != self.viewing_env_idx:
+            e = int(self.viewing_env_idx)
+            self._renderer.set_cameras([R.camera(e, self.cfg.camera_width, self.cfg.camera_height, (0.0, -4.0, 2.0),
+                                                 (0.0, 0.0, 1.0), follow_body=0, follow_mode=R.FOLLOW_POSITION_XY)])
+            self._viewed = self.viewing_env_idx
+        t = ((self.progress_buf.float() + 1.0) * (1.0 / 30.0) + self._motion_start_times
+             + self._motion_start_times_offset)
+        ms = self.engine.motion_state(self._sampled_motion_ids, t, offset=self._global_offset, want_dof=False)
+        self._marker_pos.copy_(ms["rg_pos"])
+        return self._renderer.render()[0]
 
     def close(self):
+        self._renderer = None
         self.engine = None
 
 

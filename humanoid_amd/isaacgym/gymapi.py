@@ -16,7 +16,14 @@ Engine-specific behaviour (documented, not silent):
 * all envs share one articulation, PD gains and filter table (what puffer-phc does): a
   ``set_actor_dof_properties`` / ``set_actor_rigid_shape_properties`` that differs between envs
   raises ``NotImplementedError``;
-* no viewer (headless only), CPU pipeline refused (the engine is GPU-only).
+* no viewer (headless only: ``create_viewer`` raises), CPU pipeline refused (the engine is GPU-only);
+* camera SENSORS exist (``render_env.py:151-171, 218-227, 398-411``): ``create_camera_sensor``,
+  ``set_camera_location`` / ``set_camera_transform`` / ``attach_camera_to_body``,
+  ``render_all_camera_sensors``, ``get_camera_image`` (colour, depth, segmentation) and its GPU-tensor
+  form, ``set_rigid_body_color`` / ``set_rigid_body_segmentation_id``. They are drawn by the HIP ray
+  caster (``include/humanoid_render.h`` defines the image); all cameras of a sim share one size, a
+  camera sees its own env only, optical flow is refused, and a camera transform keeps the view
+  direction but not a roll about it (the image's up is the world's).
 """
 from __future__ import annotations
 
@@ -42,6 +49,11 @@ STATE_NONE, STATE_POS, STATE_VEL, STATE_ALL = 0, 1, 2, 3
 # gymapi.CoordinateSpace (apply_rigid_body_force_tensors, render_env.py:105-126): the envs share one
 # world frame here, so ENV_SPACE and GLOBAL_SPACE are the same frame
 ENV_SPACE, LOCAL_SPACE, GLOBAL_SPACE = _abi.SPACE_ENV, _abi.SPACE_LOCAL, _abi.SPACE_GLOBAL
+
+# camera sensors (render_env.py:151-171): image types, mesh kinds, camera follow modes
+IMAGE_COLOR, IMAGE_DEPTH, IMAGE_SEGMENTATION, IMAGE_OPTICAL_FLOW = 0, 1, 2, 3
+MESH_NONE, MESH_COLLISION, MESH_VISUAL, MESH_VISUAL_AND_COLLISION = 0, 1, 2, 3
+FOLLOW_POSITION, FOLLOW_TRANSFORM = 0, 1  # include/humanoid_render.h HR_FOLLOW_*
 
 DofPropertiesDtype = np.dtype([("hasLimits", "?"), ("lower", "<f4"), ("upper", "<f4"), ("driveMode", "<i4"),
                                ("velocity", "<f4"), ("effort", "<f4"), ("stiffness", "<f4"), ("damping", "<f4"),
@@ -114,7 +126,26 @@ class PlaneParams:
 
 
 class CameraProperties:
-    pass
+    def __init__(self):
+        self.width = 1600
+        self.height = 900
+        self.horizontal_fov = 90.0
+        self.near_plane = 0.001
+        self.far_plane = 2.0e6
+        self.enable_tensors = False
+
+
+class _Camera:
+    """One camera sensor of a sim: what hr_camera holds, filled by set_camera_location /
+    set_camera_transform / attach_camera_to_body."""
+
+    def __init__(self, env_index, props: CameraProperties):
+        self.env = env_index
+        self.props = copy.copy(props)
+        self.pos = (0.0, -4.0, 2.0)
+        self.target = (0.0, 0.0, 1.0)
+        self.follow_body = -1
+        self.follow_mode = FOLLOW_POSITION
 
 
 class RigidBodyProperties:
@@ -158,6 +189,9 @@ class _Env:
     def __init__(self, index):
         self.index = index
         self.actor = None
+        self.cameras = []     # indices into sim.cameras; a camera handle is its position in this list
+        self.body_rgb = None  # [24,3] once set_rigid_body_color has touched the env
+        self.body_seg = None  # [24] from create_actor's segmentation_id / set_rigid_body_segmentation_id
 
 
 class Sim:
@@ -173,6 +207,12 @@ class Sim:
         self.start_poses = []
         self.engine = None
         self.pending_substeps = 0
+        self.cameras: List[_Camera] = []
+        self.renderer = None
+        self.cameras_dirty = True
+        self.appearance_dirty = True
+        self.appearance = (None, None)  # the device tensors the renderer reads
+        self.rendered = False
 
 
 # ----------------------------------------------------------------------------------- the Gym object
@@ -259,6 +299,7 @@ class Gym:
         elif sim.self_collision != sc:
             raise NotImplementedError("self-collision must be the same for every env")
         env.actor = name
+        env.body_seg = np.full(_abi.NB, int(segmentation_id), np.int32)  # the actor's default id
         sim.start_poses.append(((pose.p.x, pose.p.y, pose.p.z), (pose.r.x, pose.r.y, pose.r.z, pose.r.w)))
         return 0
 
@@ -429,6 +470,155 @@ class Gym:
     def fetch_results(self, sim: Sim, wait: bool = True):
         self._flush(sim)
         return True
+
+    # -- camera sensors (render_env.py:151-171, 218-227, 398-411) -------------------------------------
+    def create_camera_sensor(self, env: _Env, props: CameraProperties):
+        """A camera on ``env`` (before or after prepare_sim); the handle counts the env's cameras."""
+        sim = env.sim
+        if props.width < 1 or props.height < 1:
+            raise ValueError(f"camera size {props.width} x {props.height}")
+        if sim.cameras and (sim.cameras[0].props.width, sim.cameras[0].props.height) != (props.width, props.height):
+            raise NotImplementedError(
+                f"camera of {props.width} x {props.height} in a sim whose cameras are {sim.cameras[0].props.width} x "
+                f"{sim.cameras[0].props.height}: the cameras of one sim share one size (one launch draws them all)")
+        sim.cameras.append(_Camera(env.index, props))
+        env.cameras.append(len(sim.cameras) - 1)
+        sim.cameras_dirty = True
+        return len(env.cameras) - 1
+
+    @staticmethod
+    def _camera(env: _Env, handle) -> _Camera:
+        if not 0 <= int(handle) < len(env.cameras):
+            raise ValueError(f"env {env.index} has no camera {handle}")
+        return env.sim.cameras[env.cameras[int(handle)]]
+
+    @staticmethod
+    def _forward(t: Transform):
+        """A transform's position and the point one metre along its +X axis (the view direction of an
+        Isaac Gym camera transform)."""
+        q = np.array([t.r.x, t.r.y, t.r.z], np.float64)
+        v = np.array([1.0, 0.0, 0.0])
+        c = 2.0 * np.cross(q, v)
+        fwd = v + t.r.w * c + np.cross(q, c)
+        p = np.array([t.p.x, t.p.y, t.p.z], np.float64)
+        return tuple(p), tuple(p + fwd)
+
+    def set_camera_location(self, handle, env: _Env, pos: Vec3, target: Vec3):
+        c = self._camera(env, handle)
+        c.pos, c.target = tuple(pos), tuple(target)
+        c.follow_body = -1
+        env.sim.cameras_dirty = True
+
+    def set_camera_transform(self, handle, env: _Env, transform: Transform):
+        c = self._camera(env, handle)
+        c.pos, c.target = self._forward(transform)
+        c.follow_body = -1
+        env.sim.cameras_dirty = True
+
+    def attach_camera_to_body(self, handle, env: _Env, body: int, local_transform: Transform, mode: int):
+        """The camera follows ``body`` of the env's actor, resolved on the device at render time:
+        FOLLOW_POSITION keeps the world orientation of the offset, FOLLOW_TRANSFORM rotates with the body."""
+        if mode not in (FOLLOW_POSITION, FOLLOW_TRANSFORM):
+            raise ValueError(f"camera follow mode {mode}")
+        if not 0 <= int(body) < _abi.NB:
+            raise ValueError(f"body {body} outside [0, {_abi.NB})")
+        c = self._camera(env, handle)
+        c.pos, c.target = self._forward(local_transform)
+        c.follow_body, c.follow_mode = int(body), int(mode)
+        env.sim.cameras_dirty = True
+
+    def set_rigid_body_color(self, env: _Env, actor, body: int, mesh_type: int, color: Vec3):
+        if mesh_type not in (MESH_VISUAL, MESH_VISUAL_AND_COLLISION):
+            return  # only the visual colour is drawn
+        if not 0 <= int(body) < _abi.NB:
+            raise ValueError(f"body {body} outside [0, {_abi.NB})")
+        if env.body_rgb is None:
+            from ..render import BODY_RGB
+            env.body_rgb = np.tile(np.asarray(BODY_RGB, np.float32), (_abi.NB, 1))
+        env.body_rgb[int(body)] = tuple(color)
+        env.sim.appearance_dirty = True
+
+    def set_rigid_body_segmentation_id(self, env: _Env, actor, body: int, seg_id: int):
+        if not 0 <= int(body) < _abi.NB:
+            raise ValueError(f"body {body} outside [0, {_abi.NB})")
+        if env.body_seg is None:
+            env.body_seg = np.zeros(_abi.NB, np.int32)
+        env.body_seg[int(body)] = int(seg_id)
+        env.sim.appearance_dirty = True
+
+    def _sync_renderer(self, sim: Sim):
+        import torch
+        from .. import render as R
+        if sim.engine is None:
+            raise RuntimeError("render_all_camera_sensors before prepare_sim")
+        if not sim.cameras:
+            raise RuntimeError("render_all_camera_sensors without a camera sensor")
+        if sim.renderer is None:
+            sim.renderer = R.Renderer(sim.engine)
+        if sim.cameras_dirty:
+            sim.renderer.set_cameras([
+                R.camera(c.env, c.props.width, c.props.height, c.pos, c.target, hfov_deg=c.props.horizontal_fov,
+                         near=c.props.near_plane, far=c.props.far_plane, follow_body=c.follow_body,
+                         follow_mode=c.follow_mode) for c in sim.cameras])
+            sim.cameras_dirty = False
+        if sim.appearance_dirty:
+            dev = sim.engine.device
+            rgb = seg = None
+            if any(e.body_rgb is not None for e in sim.envs):
+                host = np.stack([e.body_rgb if e.body_rgb is not None
+                                 else np.tile(np.asarray(R.BODY_RGB, np.float32), (_abi.NB, 1)) for e in sim.envs])
+                rgb = torch.from_numpy(np.ascontiguousarray(host, np.float32)).to(dev)
+            if any(e.body_seg is not None and e.body_seg.any() for e in sim.envs):
+                host = np.stack([e.body_seg if e.body_seg is not None else np.zeros(_abi.NB, np.int32)
+                                 for e in sim.envs])
+                seg = torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(dev)
+            sim.renderer.set_appearance(rgb, seg)
+            sim.appearance = (rgb, seg)
+            sim.appearance_dirty = False
+
+    def render_all_camera_sensors(self, sim: Sim):
+        self._flush(sim)
+        self._sync_renderer(sim)
+        sim.renderer.render()
+        sim.rendered = True
+        return True
+
+    def _image(self, sim: Sim, env: _Env, handle, image_type):
+        if image_type == IMAGE_OPTICAL_FLOW:
+            raise NotImplementedError("IMAGE_OPTICAL_FLOW: the ray caster draws single frames and keeps no "
+                                      "previous-frame geometry to difference against")
+        if image_type not in (IMAGE_COLOR, IMAGE_DEPTH, IMAGE_SEGMENTATION):
+            raise ValueError(f"image type {image_type}")
+        idx = env.cameras[int(handle)] if 0 <= int(handle) < len(env.cameras) else None
+        if idx is None:
+            raise ValueError(f"env {env.index} has no camera {handle}")
+        if not sim.rendered or sim.renderer is None or idx >= sim.renderer.num_cameras:
+            raise RuntimeError("get_camera_image before render_all_camera_sensors: nothing has been drawn for "
+                               "this camera yet")
+        r = sim.renderer
+        return (r.color, r.depth, r.seg)[image_type][idx]
+
+    def get_camera_image(self, sim: Sim, env: _Env, handle, image_type):
+        """numpy copy of the last render: colour uint8 [H, W*4] (Isaac Gym's flattened RGBA rows, reshaped
+        by the caller, render_env.py:160), depth float32 [H,W], segmentation int32 [H,W]."""
+        t = self._image(sim, env, handle, image_type)
+        a = t.cpu().numpy()
+        return a.reshape(a.shape[0], -1) if image_type == IMAGE_COLOR else a
+
+    def get_camera_image_gpu_tensor(self, sim: Sim, env: _Env, handle, image_type):
+        """The renderer's own image memory ([H,W,4] u8, [H,W] f32 / i32) as a GymTensor: wrap_tensor
+        aliases it, and every later render_all_camera_sensors refreshes it in place."""
+        from . import gymtorch
+        if not sim.rendered:  # Isaac Gym hands the tensor out before the first render: draw once
+            self.render_all_camera_sensors(sim)
+        return gymtorch.unwrap_tensor(self._image(sim, env, handle, image_type))
+
+    def start_access_image_tensors(self, sim: Sim):
+        self._flush(sim)
+        return True
+
+    end_access_image_tensors = start_access_image_tensors
+    step_graphics = start_access_image_tensors
 
     # -- viewer (absent) -----------------------------------------------------------------------------
     def create_viewer(self, sim, props):

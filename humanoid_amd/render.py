@@ -1,0 +1,212 @@
+"""Headless camera sensors: ctypes shim over ``libhumanoid_render.so`` (``include/humanoid_render.h``).
+
+One HIP ray-casting kernel draws the engine's analytic scene (24 sphere / capsule / box geoms per
+env, marker spheres, the ground plane) straight from the engine's rigid-body state buffer; the
+library only reads the engine's memory. :class:`Renderer` owns the output images and launches on
+the engine's current stream. There is no CPU path and no window: without the library or a GPU
+the constructor raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import struct
+import zlib
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _abi
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_render.so")
+_lib = None
+
+# include/humanoid_render.h
+FLAG_SHADOWS, FLAG_CHECKER, FLAG_NO_CULL = 1, 2, 4
+FLAGS_DEFAULT = FLAG_SHADOWS | FLAG_CHECKER
+SEG_MARKER = 1000
+MAX_MARKERS = 24
+FOLLOW_POSITION, FOLLOW_TRANSFORM, FOLLOW_POSITION_XY = 0, 1, 2
+BODY_RGB = (0.80, 0.68, 0.52)
+
+HR_SYMBOLS = ("hr_last_error", "hr_version", "hr_create", "hr_destroy", "hr_validate_cameras", "hr_set_cameras",
+              "hr_set_appearance", "hr_set_markers", "hr_render")
+
+
+class RenderError(RuntimeError):
+    pass
+
+
+class HrCamera(C.Structure):
+    """include/humanoid_render.h hr_camera."""
+    _fields_ = [("env", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("hfov_deg", C.c_float),
+                ("near", C.c_float), ("far", C.c_float), ("follow_body", C.c_int32), ("follow_mode", C.c_int32),
+                ("pos", C.c_float * 3), ("target", C.c_float * 3)]
+
+
+def camera(env: int, width: int, height: int, pos, target, hfov_deg: float = 90.0, near: float = 0.001,
+           far: float = 2.0e6, follow_body: int = -1, follow_mode: int = FOLLOW_POSITION) -> HrCamera:
+    """One camera sensor. Fixed (``follow_body`` -1): ``pos`` / ``target`` are world points; following:
+    offsets from the body origin, rotated by the body's rotation in ``FOLLOW_TRANSFORM`` mode; in
+    ``FOLLOW_POSITION_XY`` mode only x and y follow and the heights are absolute."""
+    c = HrCamera(int(env), int(width), int(height), float(hfov_deg), float(near), float(far), int(follow_body),
+                 int(follow_mode))
+    c.pos[:] = [float(x) for x in pos]
+    c.target[:] = [float(x) for x in target]
+    return c
+
+
+def load_library(path: Optional[str] = None):
+    """Load (never build) the render library; it loads without a GPU."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise RenderError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+    lib = C.CDLL(p)
+    V, I, F = C.c_void_p, C.c_int, C.c_float
+    lib.hr_last_error.restype = C.c_char_p
+    lib.hr_last_error.argtypes = []
+    sigs = {"hr_version": [], "hr_create": [I, V, I, V], "hr_destroy": [V], "hr_validate_cameras": [V, I, I],
+            "hr_set_cameras": [V, V, I], "hr_set_appearance": [V, V, V], "hr_set_markers": [V, V, I, V, F],
+            "hr_render": [V, V, V, V, V, C.c_uint32, V]}
+    for name, args in sigs.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = I
+    _lib = lib
+    return lib
+
+
+def _check(rc):
+    if rc != 0:
+        raise RenderError(_lib.hr_last_error().decode())
+
+
+def validate_cameras(cams: Sequence[HrCamera], num_envs: int):
+    """The host-side check of a camera set (hr_validate_cameras); raises :class:`RenderError`."""
+    lib = load_library()
+    arr = (HrCamera * max(len(cams), 1))(*cams)
+    _check(lib.hr_validate_cameras(arr, len(cams), int(num_envs)))
+
+
+class Renderer:
+    """The camera sensors of one :class:`humanoid_amd.engine.Engine`.
+
+    ``set_cameras`` (re)allocates the images: ``color`` u8 [K,H,W,4] RGBA, ``depth`` f32 [K,H,W]
+    (negative view-space distance, -inf where nothing is hit), ``seg`` i32 [K,H,W]; ``render`` fills
+    them from the engine's current rigid-body state, on the engine's current stream."""
+
+    def __init__(self, engine):
+        import torch
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise RenderError("no HIP device visible: the renderer has no CPU path")
+        self.engine = engine
+        self.device = engine.device
+        self.num_envs = engine.num_envs
+        h = C.c_void_p()
+        _check(self.lib.hr_create(engine.device_index, C.byref(engine.he_model), self.num_envs, C.byref(h)))
+        self.h = h
+        self.num_cameras = 0
+        self.width = self.height = 0
+        self.color = self.depth = self.seg = None
+        self._appearance = (None, None)
+        self._markers = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and self.lib is not None:
+                self.lib.hr_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _dev(self, t, dtype, shape, what):
+        if t.device != self.device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise RenderError(f"{what}: expected contiguous {dtype} {tuple(shape)} on {self.device}, got {t.dtype} "
+                              f"{tuple(t.shape)} on {t.device}")
+        return C.c_void_p(t.data_ptr())
+
+    def set_cameras(self, cams: Sequence[HrCamera]):
+        """Replace the camera set (all of one size). A refused set raises and leaves the previous one."""
+        import torch
+        cams = list(cams)
+        arr = (HrCamera * max(len(cams), 1))(*cams)
+        _check(self.lib.hr_set_cameras(self.h, arr, len(cams)))
+        k, w, h = len(cams), int(cams[0].width), int(cams[0].height)
+        if (k, w, h) != (self.num_cameras, self.width, self.height):
+            self.color = torch.zeros(k, h, w, 4, dtype=torch.uint8, device=self.device)
+            self.depth = torch.zeros(k, h, w, dtype=torch.float32, device=self.device)
+            self.seg = torch.zeros(k, h, w, dtype=torch.int32, device=self.device)
+            self.num_cameras, self.width, self.height = k, w, h
+
+    def set_appearance(self, body_rgb=None, body_seg=None):
+        """Per-body colours f32 [N,24,3] and segmentation ids i32 [N,24] (device tensors, read at render
+        time, so later in-place writes show); ``None``: the default colour / id 0."""
+        import torch
+        n = self.num_envs
+        p_rgb = None if body_rgb is None else self._dev(body_rgb, torch.float32, (n, _abi.NB, 3), "body_rgb")
+        p_seg = None if body_seg is None else self._dev(body_seg, torch.int32, (n, _abi.NB), "body_seg")
+        _check(self.lib.hr_set_appearance(self.h, p_rgb, p_seg))
+        self._appearance = (body_rgb, body_seg)  # keep alive while attached
+
+    def set_markers(self, pos=None, rgb=None, radius: float = 0.05):
+        """Marker spheres: ``pos`` f32 [N,m,3] world points (device tensor, read at render time), ``rgb``
+        [m,3] host values; ``pos=None`` removes them. Markers cast no shadow and carry ``SEG_MARKER``."""
+        import torch
+        if pos is None:
+            _check(self.lib.hr_set_markers(self.h, None, 0, None, 0.0))
+            self._markers = None
+            return
+        if pos.dim() != 3:
+            raise RenderError(f"marker positions must be [num_envs, m, 3], got {tuple(pos.shape)}")
+        m = int(pos.shape[1])
+        p = self._dev(pos, torch.float32, (self.num_envs, m, 3), "marker positions")
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(rgb, np.float32), (m, 3)))
+        _check(self.lib.hr_set_markers(self.h, p, m, c.ctypes.data_as(C.c_void_p), float(radius)))
+        self._markers = pos  # keep alive while attached
+
+    def render_into(self, color=None, depth=None, seg=None, flags: int = FLAGS_DEFAULT, rb_state=None):
+        """hr_render into caller tensors (``None``: that output is not written). ``rb_state`` defaults to
+        the engine's live buffer."""
+        rb = self.engine.rb_state if rb_state is None else rb_state
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _check(self.lib.hr_render(self.h, C.c_void_p(rb.data_ptr()), vp(color), vp(depth), vp(seg), int(flags),
+                                  self.engine.stream))
+
+    def render(self, flags: int = FLAGS_DEFAULT):
+        """Draw every camera into ``color`` / ``depth`` / ``seg`` (one launch, no host synchronisation)."""
+        if self.color is None:
+            raise RenderError("render before set_cameras")
+        self.render_into(self.color, self.depth, self.seg, flags)
+        return self.color
+
+
+# ----------------------------------------------------------------------------------- files
+def save_png(path, rgba):
+    """Write an image [H,W,4] (or [H,W,3]) uint8 as a PNG (zlib + struct only)."""
+    a = np.ascontiguousarray(np.asarray(rgba))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError(f"save_png takes uint8 [H,W,3|4], got {a.dtype} {a.shape}")
+    h, w, ch = a.shape
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), a.reshape(h, w * ch)], axis=1).tobytes()  # filter 0 per row
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 6 if ch == 4 else 2, 0, 0, 0)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def write_video(path, frames, fps: int = 30):
+    """Write RGBA / RGB frames with ``imageio`` when it is installed (not a dependency of the engine)."""
+    try:
+        import imageio
+    except ImportError as e:
+        raise RenderError("write_video needs imageio; save_png writes single frames without it") from e
+    with imageio.get_writer(path, fps=fps, macro_block_size=None) as w:
+        for fr in frames:
+            w.append_data(np.asarray(fr)[..., :3])
