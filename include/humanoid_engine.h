@@ -28,7 +28,11 @@ extern "C" {
 #define HE_NUM_GEN 75          /* 6 root + 69 joint generalized velocities */
 #define HE_MAX_PAIRS 256
 #define HE_STAMP_SLOTS 32 /* diagnostic per-phase cycle slots per env (he_set_debug_stamps) */
-#define HE_MAX_CONTACTS 40       /* contact slots (points, joint limits) per env */
+#define HE_MAX_CONTACTS 40       /* contact slots (points, joint limits) per env. When the generated
+                                    contacts pass the slots or HE_MAX_ROWS, the deepest-first reduction
+                                    ranks a pool of the first 128 terrain and self candidates in slot
+                                    order (joint limits not counted); a candidate past the pool is
+                                    counted as generated and never kept (DESIGN §5 "Capacity") */
 #define HE_MAX_ROWS 63           /* solver rows per env, one per lane of a 64-lane wave: a joint limit
                                     1, a point 1 normal row, its friction on its patch (patch friction:
                                     2 tangential rows per body-terrain patch and, from 2 points on, 1

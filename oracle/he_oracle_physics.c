@@ -32,6 +32,12 @@ typedef double R;
  * (tests/diag/truncation_effect.py); the warm-start cache holds HE_MAX_ROWS rows. */
 #define MAXC 64
 #define MAXROW (3 * MAXC)
+/* The candidate pool of the deepest-first reduction (DESIGN §5 "Capacity"; the kernel's kCand): the
+ * first POOL terrain and self candidates in slot order are ranked, the joint-limit slots do not count
+ * against it, and a candidate past it is counted as generated and never kept. A property of the
+ * engine, apart from MAXC, the oracle's own solve capacity. */
+#define POOL 128
+#define MAXGEN (MAXC + POOL) /* slots gen_all may fill: the limits, then the pool */
 
 /* Sensitivity probes (tests/test_gpu_parity.py _cond_close): rounding-level noise on the Delassus
  * operator and the contact right-hand side, A_rc (1 + rel xi), b_r (1 + rel xi) with xi uniform in
@@ -487,7 +493,8 @@ static int rows_of(const contact* cs, int nc) {
 }
 
 /* Contact slots: joint limits, terrain (bodies in order, box corners deepest-first), self pairs.
- * All are generated (up to the oracle's own MAXC). When they exceed max_contacts slots or
+ * All are generated (the limits up to the oracle's own MAXC, then terrain and self candidates up to
+ * the pool of POOL; what lies past the pool is counted only). When they exceed max_contacts slots or
  * HE_MAX_ROWS rows, the limits are kept and the contacts are taken deepest first (smallest gap,
  * ties in slot order), each one kept while its rows still fit (3 for a self pair or a body's first
  * terrain point, 2 for its second -- the normal and the patch's torsional row -- 1 after), and the
@@ -506,6 +513,23 @@ void ho_set_row_weight_out(float* out) { g_roww_out = out; }
 /* diagnostic (tests/diag): the gap of every solver row's contact of the last substep, [N, HE_MAX_ROWS] */
 static float* g_rowgap_out;
 void ho_set_row_gap_out(float* out) { g_rowgap_out = out; }
+/* diagnostic (tests): the kept contact slots of the last substep, [N, MAXC, 8] doubles per slot: world
+ * contact point (3), normal (3), gap, 16-bit key of the slot's normal row (a limit slot: point 0,
+ * normal +z, its angle gap); slots past the count are zero with key -1 */
+static double* g_contact_out;
+void ho_set_contact_out(double* out) { g_contact_out = out; }
+static void contacts_out(const contact* cs, int nc) {
+    if (!g_contact_out) return;
+    double* o = g_contact_out + (size_t)g_probe_env * MAXC * 8;
+    for (int i = 0; i < MAXC; ++i, o += 8) {
+        memset(o, 0, 8 * sizeof(double));
+        o[7] = -1;
+        if (i >= nc) continue;
+        for (int c = 0; c < 3; ++c) { o[c] = cs[i].x[c]; o[3 + c] = cs[i].n[c]; }
+        o[6] = cs[i].gap;
+        o[7] = cs[i].key;
+    }
+}
 static int gen_contacts(const he_model* m, const he_sim_params* p, const kin* k, const env_state* s, int terrain_kind,
                         R mu, contact* cs, int* total) {
     int nlim = 0;
@@ -516,13 +540,13 @@ static int gen_contacts(const he_model* m, const he_sim_params* p, const kin* k,
     const int maxr = big ? MAXROW : HE_MAX_ROWS;
     if (nc <= maxc && rows_of(cs, nc) <= maxr) return nc;
     const int klim = nlim < maxc ? nlim : maxc; /* limits first, one row each */
-    int order[MAXC], no = 0;
+    int order[POOL], no = 0;
     for (int i = nlim; i < nc; ++i) {
         int j = no++; /* insertion by (gap, slot) */
         while (j > 0 && (cs[order[j - 1]].gap > cs[i].gap)) { order[j] = order[j - 1]; --j; }
         order[j] = i;
     }
-    int kept[MAXC] = {0}, pc[NB] = {0};
+    int kept[MAXGEN] = {0}, pc[NB] = {0};
     int rows = klim, slots = klim;
     for (int q = 0; q < no; ++q) {
         const int i = order[q];
@@ -627,6 +651,7 @@ static int gen_all(const he_model* m, const he_sim_params* p, const kin* k, cons
     *total = 0;
     int nc = p->joint_limits ? gen_limits(m, p, s, cs, maxc, total) : 0;
     *nlim_out = nc;
+    maxc = nc + POOL; /* the pool holds terrain and self candidates only */
     R off = p->contact_offset;
     for (int b = 0; b < NB; ++b) {
         const float* g = m->geom_params[b];
@@ -949,7 +974,7 @@ static void substep(const he_model* m, const topo* t, const he_sim_params* p, en
     static __thread R H[NG][NG];
     static __thread R Z[MAXROW][NG];
     static __thread R A[MAXROW][MAXROW];
-    static __thread contact cs[MAXC];
+    static __thread contact cs[MAXGEN];
     const R dt = p->dt;
     sinertia I[NB];
     R bias[NG];
@@ -1025,6 +1050,7 @@ static void substep(const he_model* m, const topo* t, const he_sim_params* p, en
     /* contacts */
     int total = 0;
     int nc = gen_contacts(m, p, &k, s, terrain_kind, mu, cs, &total);
+    contacts_out(cs, nc);
     out->num_contacts = nc;
     out->dropped = total - nc;
     out->residual = 0;
@@ -1263,7 +1289,7 @@ static void substep_tgs(const he_model* m, const topo* t, const he_sim_params* p
     static __thread R H[NG][NG];
     static __thread R Z[MAXROW][NG], J[MAXROW][NG];
     static __thread R A[MAXROW][MAXROW];
-    static __thread contact cs[MAXC];
+    static __thread contact cs[MAXGEN];
     static __thread srow rows[MAXROW];
     const R dt = p->dt;
     const int K = p->solver_iterations < 1 ? 1 : (p->solver_iterations > TGS_MAXIT ? TGS_MAXIT : p->solver_iterations);
@@ -1301,6 +1327,7 @@ static void substep_tgs(const he_model* m, const topo* t, const he_sim_params* p
     /* the step's contact set and rows (at the step's start) */
     int total = 0;
     const int nc = gen_contacts(m, p, &k, s, terrain_kind, mu, cs, &total);
+    contacts_out(cs, nc);
     out->num_contacts = nc;
     out->dropped = total - nc;
     out->residual = 0;

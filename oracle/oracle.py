@@ -190,6 +190,18 @@ def set_row_gap_out(arr=None):
     lib().ho_set_row_gap_out(None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_float)))
 
 
+CONTACT_OUT_SLOTS = 64  # he_oracle_physics.c MAXC, the oracle's own slot capacity
+
+
+def set_contact_out(arr=None):
+    """Diagnostics only: float64 [N, CONTACT_OUT_SLOTS, 8] filled with the kept contact slots of each
+    env's last substep: world point (3), normal (3), gap, the 16-bit key of the slot's normal row (-1
+    past the slot count; a joint-limit slot: zero point, +z, its angle gap); None turns it off."""
+    if arr is not None:
+        assert arr.dtype == np.float64 and arr.flags.c_contiguous and arr.shape[1:] == (CONTACT_OUT_SLOTS, 8)
+    lib().ho_set_contact_out(None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_double)))
+
+
 def physics_step(model: "_abi.HeModel", sim: "_abi.HeSimParams", root_states, dof_state, targets, substeps=2,
                  mass_scale=None, friction=None, terrain_kind=None, cache=None):
     """In-place on root_states [N,13] / dof_state [N,69,2] (float32 arrays) and on the warm-start
