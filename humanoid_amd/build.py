@@ -1,5 +1,6 @@
-"""Build ``humanoid_amd/libhumanoid_engine.so`` (with its diagnostic twin) and the camera-sensor
-library ``humanoid_amd/libhumanoid_render.so`` for gfx950 with hipcc (in-tree, they travel with the
+"""Build ``humanoid_amd/libhumanoid_engine.so`` (with its diagnostic twin), the camera-sensor
+library ``humanoid_amd/libhumanoid_render.so`` and the dynamics-query library
+``humanoid_amd/libhumanoid_dynamics.so`` for gfx950 with hipcc (in-tree, they travel with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
 import hashlib
 import os
@@ -18,6 +19,10 @@ PHASES_DEFS = {"he_physics.hip": ["-DHE_PHASE_STAMPS=1"]}
 # engine's buffers, so the engine's device code (device_code_id) does not move with it
 RENDER_LIB = os.path.join(HERE, "libhumanoid_render.so")
 RENDER_SOURCES = [("hr_render.hip", [])]
+# the dynamics-query tensors (include/humanoid_dynamics.h: Jacobians, mass matrix, bias force): likewise
+# a library of its own that only reads the engine's state buffers
+DYNAMICS_LIB = os.path.join(HERE, "libhumanoid_dynamics.so")
+DYNAMICS_SOURCES = [("hd_dynamics.hip", [])]
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("HE_OFFLOAD_ARCH", "gfx950")
 
@@ -38,7 +43,8 @@ SOURCES = [
 ]
 HEADERS = ["he_kernels.h", "he_math.h", "he_imitation_env.h", "he_topo.h", "he_regla.h", "he_smpl_topo.h", os.path.join("..", "..", "include", "humanoid_engine.h"),
            os.path.join("..", "..", "include", "humanoid_rollout.h"),
-           os.path.join("..", "..", "include", "humanoid_render.h")]
+           os.path.join("..", "..", "include", "humanoid_render.h"),
+           os.path.join("..", "..", "include", "humanoid_dynamics.h")]
 
 
 def _hipcc():
@@ -59,8 +65,9 @@ MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2)}
 # that lists fewer fails the build, so neither can drop out of the check unnoticed
 MIN_KERNELS = {"he_physics.hip": 2}
 # kernels that must not touch scratch memory (no spilled registers, no stack): the render kernel keeps
-# its primitives in LDS and everything else in registers
-NO_SCRATCH = {"hr_render.hip": "render_kernel"}
+# its primitives in LDS and everything else in registers; the dynamics kernel keeps its matrices in
+# named registers and indexes only LDS
+NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_kernel"}
 
 
 def _check_scratch(src, stderr):
@@ -173,14 +180,15 @@ def build(force=False, verbose=False):
             cmd = [hipcc] + common + [cuid] + flags + defs.get(src, []) + ["-c", s, "-o", o]
             _compile(hipcc, cmd, s, o, force and lib == LIB or force and src in defs, hdr_time, verbose)
         _link(hipcc, lib, objs, force)
-    objs = []
-    for src, flags in RENDER_SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(BUILD, src + ".o")
-        objs.append(o)
-        cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
-        _compile(hipcc, [hipcc] + common + [cuid] + flags + ["-c", s, "-o", o], s, o, force, hdr_time, verbose)
-    _link(hipcc, RENDER_LIB, objs, force)
+    for lib, sources in ((RENDER_LIB, RENDER_SOURCES), (DYNAMICS_LIB, DYNAMICS_SOURCES)):
+        objs = []
+        for src, flags in sources:
+            s = os.path.join(CSRC, src)
+            o = os.path.join(BUILD, src + ".o")
+            objs.append(o)
+            cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
+            _compile(hipcc, [hipcc] + common + [cuid] + flags + ["-c", s, "-o", o], s, o, force, hdr_time, verbose)
+        _link(hipcc, lib, objs, force)
     return LIB
 
 

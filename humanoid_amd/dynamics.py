@@ -1,0 +1,167 @@
+"""Dynamics-query tensors: ctypes shim over ``libhumanoid_dynamics.so`` (``include/humanoid_dynamics.h``).
+
+One HIP kernel forms, for the state the engine is in, the body Jacobians ``[N,24,6,75]``, the
+joint-space inertia ``[N,75,75]`` and the gravity / Coriolis force ``[N,75]`` of every env from the
+engine's root-state and dof-state buffers alone (its own forward kinematics, so it is right
+immediately after an indexed state write); the library only reads the engine's memory.
+:class:`Dynamics` owns the three output tensors and launches on the engine's current stream. There is
+no CPU path: without the library or a GPU the constructor raises.
+
+Columns follow Isaac Gym's floating-base order: root linear velocity 3, root angular velocity 3, the
+69 dof velocities. The dof velocities are the engine's child-frame relative rates of the exp-map ball
+joints, not derivatives of the exp-map coordinates (the header has the definitions).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+from . import _abi
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_dynamics.so")
+_lib = None
+
+# include/humanoid_dynamics.h
+FLAG_ARMATURE, FLAG_NO_GRAVITY = 1, 2
+FLAGS_DEFAULT = FLAG_ARMATURE
+JAC_ROWS = 6
+NG = 75  # HE_NUM_GEN: 6 root + 69 dof generalised velocities
+
+HD_SYMBOLS = ("hd_last_error", "hd_version", "hd_validate_model", "hd_create", "hd_destroy", "hd_compute")
+
+
+class DynamicsError(RuntimeError):
+    pass
+
+
+def load_library(path: Optional[str] = None):
+    """Load (never build) the dynamics library; it loads without a GPU."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise DynamicsError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+    lib = C.CDLL(p)
+    V, I = C.c_void_p, C.c_int
+    lib.hd_last_error.restype = C.c_char_p
+    lib.hd_last_error.argtypes = []
+    sigs = {"hd_version": [], "hd_validate_model": [V], "hd_create": [I, V, V, I, V], "hd_destroy": [V],
+            "hd_compute": [V, V, V, V, V, V, C.c_uint32, V]}
+    for name, args in sigs.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = I
+    _lib = lib
+    return lib
+
+
+def _check(rc):
+    if rc != 0:
+        raise DynamicsError(_lib.hd_last_error().decode())
+
+
+def validate_model(he_model: _abi.HeModel):
+    """The host-side model check of hd_create (hd_validate_model); raises :class:`DynamicsError`."""
+    lib = load_library()
+    _check(lib.hd_validate_model(C.byref(he_model)))
+
+
+def check_tensor(t, dtype, shape, device, what):
+    """The check every tensor passes before its pointer is handed to the library: a contiguous tensor
+    of this dtype and shape on this device, else :class:`DynamicsError`. Returns the device pointer."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise DynamicsError(f"{what}: expected a torch tensor, got {type(t).__name__}")
+    if t.device != device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise DynamicsError(f"{what}: expected contiguous {dtype} {tuple(shape)} on {device}, got "
+                            f"{'contiguous' if t.is_contiguous() else 'non-contiguous'} {t.dtype} {tuple(t.shape)} "
+                            f"on {t.device}")
+    return C.c_void_p(t.data_ptr())
+
+
+def output_shapes(num_envs: int):
+    n = int(num_envs)
+    return {"jacobian": (n, _abi.NB, JAC_ROWS, NG), "mass_matrix": (n, NG, NG), "bias": (n, NG)}
+
+
+class Dynamics:
+    """The dynamics-query tensors of one :class:`humanoid_amd.engine.Engine`.
+
+    ``jacobian`` f32 [N,24,6,75] (rows: body-origin linear velocity, world angular velocity),
+    ``mass_matrix`` f32 [N,75,75] and ``bias`` f32 [N,75] are allocated once and refreshed in place
+    (views stay valid). ``armature`` (default on: the inertia the engine's own solve uses) puts the
+    model's dof armature on the mass matrix's diagonal; ``gravity`` (default on) keeps gravity in the
+    bias force. Gravity is the engine's ``sim_params.gravity``."""
+
+    def __init__(self, engine, armature: bool = True):
+        import torch
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise DynamicsError("no HIP device visible: the dynamics kernel has no CPU path")
+        self.engine = engine  # keeps the engine (and the buffers the kernel reads) alive
+        self.device = engine.device
+        self.num_envs = engine.num_envs
+        self.armature = bool(armature)
+        self.gravity = True
+        g = (C.c_float * 3)(*[float(x) for x in engine.params.gravity])
+        h = C.c_void_p()
+        _check(self.lib.hd_create(engine.device_index, C.byref(engine.he_model), g, self.num_envs, C.byref(h)))
+        self.h = h
+        shapes = output_shapes(self.num_envs)
+        self.jacobian = torch.zeros(shapes["jacobian"], dtype=torch.float32, device=self.device)
+        self.mass_matrix = torch.zeros(shapes["mass_matrix"], dtype=torch.float32, device=self.device)
+        self.bias = torch.zeros(shapes["bias"], dtype=torch.float32, device=self.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and self.lib is not None:
+                self.lib.hd_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @property
+    def flags(self) -> int:
+        return (FLAG_ARMATURE if self.armature else 0) | (0 if self.gravity else FLAG_NO_GRAVITY)
+
+    def refresh_into(self, jacobian=None, mass_matrix=None, bias=None, flags: Optional[int] = None, root_state=None,
+                     dof_state=None):
+        """hd_compute into caller tensors (``None``: that output is not computed). The states default to
+        the engine's live root-state / dof-state buffers. Every tensor is checked (shape, dtype, device,
+        contiguity) before any pointer is passed."""
+        import torch
+        n = self.num_envs
+        shapes = output_shapes(n)
+        if jacobian is None and mass_matrix is None and bias is None:
+            raise DynamicsError("refresh: no output asked for")
+        f32 = torch.float32
+        p_jac = None if jacobian is None else check_tensor(jacobian, f32, shapes["jacobian"], self.device, "jacobian")
+        p_mass = None if mass_matrix is None else check_tensor(mass_matrix, f32, shapes["mass_matrix"], self.device,
+                                                               "mass_matrix")
+        p_bias = None if bias is None else check_tensor(bias, f32, shapes["bias"], self.device, "bias")
+        root = self.engine.root_states if root_state is None else root_state
+        dof = self.engine.dof_state if dof_state is None else dof_state
+        p_root = check_tensor(root, f32, (n, 13), self.device, "root_state")
+        p_dof = check_tensor(dof, f32, (n * _abi.ND, 2), self.device, "dof_state")
+        _check(self.lib.hd_compute(self.h, p_root, p_dof, p_jac, p_mass, p_bias,
+                                   int(self.flags if flags is None else flags), self.engine.stream))
+
+    def refresh(self, jacobian: bool = True, mass_matrix: bool = True, bias: bool = True):
+        """Recompute what is asked from the engine's current state: one launch on the current stream, no
+        host synchronisation, in place."""
+        self.refresh_into(self.jacobian if jacobian else None, self.mass_matrix if mass_matrix else None,
+                          self.bias if bias else None)
+
+    def generalized_velocity(self):
+        """qd [N,75] of the engine's current state: root linear velocity, root angular velocity, the 69
+        dof velocities (a torch gather; defining property: ``jacobian @ qd == rb_state[..., 7:13]``)."""
+        import torch
+        e = self.engine
+        return torch.cat([e.root_states[:, 7:13], e.dof_state.view(self.num_envs, _abi.ND, 2)[:, :, 1]], dim=1)
+
+    def inverse_dynamics(self, qdd):
+        """tau = mass_matrix @ qdd + bias for qdd [N,75], from the tensors as last refreshed (a torch
+        one-liner, no kernel of its own)."""
+        return (self.mass_matrix @ qdd.unsqueeze(-1)).squeeze(-1) + self.bias

@@ -23,7 +23,15 @@ Engine-specific behaviour (documented, not silent):
   form, ``set_rigid_body_color`` / ``set_rigid_body_segmentation_id``. They are drawn by the HIP ray
   caster (``include/humanoid_render.h`` defines the image); all cameras of a sim share one size, a
   camera sees its own env only, optical flow is refused, and a camera transform keeps the view
-  direction but not a roll about it (the image's up is the world's).
+  direction but not a roll about it (the image's up is the world's);
+* the dynamics-query tensors exist: ``acquire_jacobian_tensor`` [N,24,6,75] and
+  ``acquire_mass_matrix_tensor`` [N,75,75] with ``refresh_jacobian_tensors`` /
+  ``refresh_mass_matrix_tensors``, formed by one HIP kernel from the root and dof state
+  (``include/humanoid_dynamics.h`` has the definitions). Columns are Isaac Gym's floating-base order
+  (root linear 3, root angular 3, the 69 dofs); the dof columns refer to the engine's child-frame
+  relative rates of the exp-map ball joints, and the mass matrix carries the dof armature, as the
+  engine's own solve does. ENGINE EXTENSION (not in Isaac Gym): ``acquire_bias_force_tensor`` [N,75]
+  / ``refresh_bias_force_tensors``, the gravity + Coriolis force c of ``M qdd + c = tau``.
 """
 from __future__ import annotations
 
@@ -213,6 +221,8 @@ class Sim:
         self.appearance_dirty = True
         self.appearance = (None, None)  # the device tensors the renderer reads
         self.rendered = False
+        self.dynamics = None          # humanoid_amd.dynamics.Dynamics, created by the first acquire
+        self.dynamics_acquired = set()  # of "jacobian", "mass_matrix", "bias"
 
 
 # ----------------------------------------------------------------------------------- the Gym object
@@ -405,6 +415,48 @@ class Gym:
 
     def acquire_force_sensor_tensor(self, sim):
         raise NotImplementedError("force sensors are not used by puffer-phc")
+
+    # -- dynamics-query tensors -------------------------------------------------------------------
+    def _acquire_dynamics(self, sim: Sim, actor_name: str, which: str):
+        if sim.engine is None:
+            raise RuntimeError(f"acquire_{which}_tensor before prepare_sim")
+        if not any(env.actor == actor_name for env in sim.envs):
+            raise ValueError(f"no env has an actor named {actor_name!r}")
+        if sim.dynamics is None:
+            from ..dynamics import Dynamics
+            sim.dynamics = Dynamics(sim.engine)
+        sim.dynamics_acquired.add(which)
+        t = getattr(sim.dynamics, which)
+        return GymTensor(t.data_ptr(), t.shape, 1, sim.device, owner=t)
+
+    def acquire_jacobian_tensor(self, sim: Sim, actor_name: str):
+        """[N,24,6,75]: per body the rows (origin linear velocity 3, world angular velocity 3) over the
+        columns (root linear 3, root angular 3, 69 dof rates). Filled by ``refresh_jacobian_tensors``."""
+        return self._acquire_dynamics(sim, actor_name, "jacobian")
+
+    def acquire_mass_matrix_tensor(self, sim: Sim, actor_name: str):
+        """[N,75,75], the joint-space inertia with the dof armature. Filled by
+        ``refresh_mass_matrix_tensors``."""
+        return self._acquire_dynamics(sim, actor_name, "mass_matrix")
+
+    def acquire_bias_force_tensor(self, sim: Sim, actor_name: str):
+        """Engine extension: [N,75], the gravity + Coriolis force. Filled by ``refresh_bias_force_tensors``."""
+        return self._acquire_dynamics(sim, actor_name, "bias")
+
+    def _refresh_dynamics(self, sim: Sim, which: str):
+        if which in sim.dynamics_acquired:  # before its acquire: a no-op, as in Isaac Gym
+            self._flush(sim)
+            sim.dynamics.refresh(jacobian=which == "jacobian", mass_matrix=which == "mass_matrix", bias=which == "bias")
+        return True
+
+    def refresh_jacobian_tensors(self, sim: Sim):
+        return self._refresh_dynamics(sim, "jacobian")
+
+    def refresh_mass_matrix_tensors(self, sim: Sim):
+        return self._refresh_dynamics(sim, "mass_matrix")
+
+    def refresh_bias_force_tensors(self, sim: Sim):
+        return self._refresh_dynamics(sim, "bias")
 
     def _flush(self, sim: Sim):
         if sim.pending_substeps:
