@@ -48,6 +48,10 @@ FORCE_PROTOTYPES = {
     "he_apply_body_forces": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "he_apply_body_forces_at_pos": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
 }
+# the solve probe: factor, y, n, out, stream
+PROBE_PROTOTYPES = {
+    "he_probe_masked_solves": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+}
 
 
 class HeModel(C.Structure):

@@ -38,6 +38,7 @@ SOURCES = [
                         "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
     ("he_ingest.hip", []),
     ("he_forces.hip", []),
+    ("he_probe.hip", []),  # tests' probe of the vector solves (he_regla.h) in both forms
     ("he_rollout.hip", ["-ffp-contract=off"]),  # GAE: the Cython module's float32 rounding
     ("he_engine.cpp", ["-x", "hip"]),
 ]

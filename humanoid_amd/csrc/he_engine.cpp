@@ -848,6 +848,13 @@ int he_set_debug_stamps(he_engine* h, uint64_t* device_buffer) {
     return 0;
 }
 
+int he_probe_masked_solves(const float* factor, const float* y, int n, float* out, void* stream) {
+    if (!factor || !y || !out) return fail("he_probe_masked_solves: null buffer");
+    if (n < 0) return fail("he_probe_masked_solves: n = %d", n);
+    HE_CHECK(launch_masked_solve_probe(factor, y, n, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 float he_hash_uniform(uint64_t seed, uint64_t step, uint32_t env) {
     uint64_t z = seed * 0x9E3779B97F4A7C15ull ^ (step + 0x632BE59BD9B4E019ull) * 0xBF58476D1CE4E5B9ull ^
                  ((uint64_t)env + 0x2545F4914F6CDD1Dull) * 0x94D049BB133111EBull;

@@ -163,6 +163,9 @@ hipError_t warm_physics_kernels(hipStream_t stream, int mode);
 hipError_t warm_ingest_kernels(hipStream_t stream, int mode);
 hipError_t warm_forces_kernels(hipStream_t stream, int mode);
 bool physics_phase_stamps();  // built with HE_PHASE_STAMPS (diagnostic twin library)
+// Test probe (he_probe.hip): the vector solves y <- L^-T y and y <- L^-1 y of he_regla.h, one wave per
+// vector, with their masked updates under EXEC and as selects: out[4][n][75]
+hipError_t launch_masked_solve_probe(const float* factor, const float* y, int n, float* out, hipStream_t stream);
 hipError_t launch_ingest(const float* pose, const float* trans, const int32_t* parents, const float* local_pos,
                          const int64_t* starts, const int64_t* nframes, const float* dt, int num_clips, int64_t F,
                          float* hot, float* cold, float* gav_raw, hipStream_t stream);

@@ -132,6 +132,73 @@ __device__ __forceinline__ void pk_fnma(f2v& z, f2v a, f2v b) {
                      : "+v"(z) : "v"(a), "v"(b));
 }
 
+// ---------------------------------------------------------------- updates under EXEC
+// The vector solves' lane-masked updates `if (lanes<C>()) y -= l * s` as the FMA alone, issued with
+// EXEC = C, instead of an all-lane FMA and a v_cndmask on the mask (two dependent VALU instructions
+// and the pad after the asm-written mask). HE_EXEC_LT / HE_EXEC_L = 0 make the select form
+// the default of the L^-T / L^-1 solve (the A/B and bit-identity partners, tools/build_variant.py);
+// the solves take the form as a template argument, so he_probe.hip runs both side by side.
+#ifndef HE_EXEC_LT
+#define HE_EXEC_LT 1
+#endif
+#ifndef HE_EXEC_L
+#define HE_EXEC_L 1
+#endif
+// how a statement writes the compile-time mask C to EXEC: 0 not at all (C empty), 1 a run of lanes
+// by s_bfm_b64 exec, a = length, b = first lane (descendant sets are runs in the DFS dof order),
+// 2 lanes < 31 only by one s_mov_b64 of a non-negative 32-bit literal (zero-extended), 3 the two halves
+template <uint64_t C>
+struct ExecMask {
+    static constexpr int kOff = C == 0 ? 0 : __builtin_ctzll(C);
+    static constexpr int kLen = C == 0 ? 0 : 64 - __builtin_clzll(C) - kOff;
+    static constexpr bool kRun = C != 0 && kLen < 64 && C == (((1ull << kLen) - 1ull) << kOff);
+    static constexpr int mode = C == 0 ? 0 : (kRun ? 1 : (C < 0x80000000ull ? 2 : 3));
+    static constexpr int a = mode == 1 ? kLen : (int)(uint32_t)C;
+    static constexpr int b = mode == 1 ? kOff : (int)(uint32_t)(C >> 32);
+};
+// slot n of a statement: yl -= l_n * s_n on the lanes of G::lo(n), then y2 -= k_n * s_n on the lanes of
+// G::hi(n), s_n a wave-uniform multiplier in an SGPR (a v_readlane result; the one constant-bus
+// operand of the FMA). The assembler's .if drops what a slot's empty mask does not need.
+#define HE_XMASK(m, a, b)                                                          \
+    ".if %[" #m "] == 1\n s_bfm_b64 exec, %[" #a "], %[" #b "]\n"                  \
+    ".elseif %[" #m "] == 2\n s_mov_b64 exec, %[" #a "]\n"                         \
+    ".elseif %[" #m "] == 3\n s_mov_b32 exec_lo, %[" #a "]\n s_mov_b32 exec_hi, %[" #b "]\n.endif\n"
+#define HE_XSLOT(n)                                                                               \
+    HE_XMASK(m##n, a##n, b##n) ".if %[m" #n "] != 0\n v_fma_f32 %[yl], -%[l" #n "], %[s" #n "], %[yl]\n.endif\n" \
+    HE_XMASK(h##n, c##n, d##n) ".if %[h" #n "] != 0\n v_fma_f32 %[y2], -%[k" #n "], %[s" #n "], %[y2]\n.endif\n"
+// an operand of an empty half is never read: it takes the other half's register
+#define HE_XOPS(n)                                                                                       \
+    [l##n] "v"(G::lo(n) != 0 ? l[n] : k[n]), [k##n] "v"(G::hi(n) != 0 ? k[n] : l[n]), [s##n] "s"(s[n]),   \
+    [m##n] "i"(ExecMask<G::lo(n)>::mode), [a##n] "i"(ExecMask<G::lo(n)>::a), [b##n] "i"(ExecMask<G::lo(n)>::b), \
+    [h##n] "i"(ExecMask<G::hi(n)>::mode), [c##n] "i"(ExecMask<G::hi(n)>::a), [d##n] "i"(ExecMask<G::hi(n)>::b)
+#define HE_XOUT [yl] "+v"(yl), [y2] "+v"(y2)
+// G::N (1..5) slots back to back in ONE statement, in slot order, EXEC restored once at its end: between
+// two statements the compiler may place copies and spill code that need every lane. EXEC must be
+// all ones on entry: the workgroup is one full wave and every branch around the solves is taken
+// by the whole wave, so the restore is the constant. The restore is also the wait state between the
+// last FMA and a v_readlane of its result, which the compiler does not see and would not pad.
+template <class G>
+__device__ __forceinline__ void fnma_lanes(float& yl, float& y2, const float (&l)[G::N], const float (&k)[G::N],
+                                           const float (&s)[G::N]) {
+    static_assert(G::N >= 1 && G::N <= 5, "a statement has one to five slots");
+    if constexpr (G::N == 1)
+        asm volatile(HE_XSLOT(0) "s_mov_b64 exec, -1" : HE_XOUT : HE_XOPS(0));
+    else if constexpr (G::N == 2)
+        asm volatile(HE_XSLOT(0) HE_XSLOT(1) "s_mov_b64 exec, -1" : HE_XOUT : HE_XOPS(0), HE_XOPS(1));
+    else if constexpr (G::N == 3)
+        asm volatile(HE_XSLOT(0) HE_XSLOT(1) HE_XSLOT(2) "s_mov_b64 exec, -1" : HE_XOUT : HE_XOPS(0), HE_XOPS(1), HE_XOPS(2));
+    else if constexpr (G::N == 4)
+        asm volatile(HE_XSLOT(0) HE_XSLOT(1) HE_XSLOT(2) HE_XSLOT(3) "s_mov_b64 exec, -1"
+                     : HE_XOUT : HE_XOPS(0), HE_XOPS(1), HE_XOPS(2), HE_XOPS(3));
+    else
+        asm volatile(HE_XSLOT(0) HE_XSLOT(1) HE_XSLOT(2) HE_XSLOT(3) HE_XSLOT(4) "s_mov_b64 exec, -1"
+                     : HE_XOUT : HE_XOPS(0), HE_XOPS(1), HE_XOPS(2), HE_XOPS(3), HE_XOPS(4));
+}
+#undef HE_XOUT
+#undef HE_XOPS
+#undef HE_XSLOT
+#undef HE_XMASK
+
 // ---------------------------------------------------------------- LTDL factorisation and solves
 // ---------------------------------------------------------------- per-lane z <- L^-T z (each lane its own rhs)
 // the packed row K (D entries) as registers: ceil(D/4) 16-byte LDS broadcasts
@@ -282,23 +349,60 @@ __device__ __forceinline__ void level_pick(float yl, float y2, float& t1, float&
         level_pick<D, J + 1, F1 && kDescLo[K] == 0, F2 && kDescHi[K] == 0>(yl, y2, t1, t2);
     }
 }
-// y <- L^-1 y by depth levels, shallowest first: the dofs of one level have disjoint descendant
-// sets, so a level is n readlanes + n selects + ONE fma with the row entry at that depth
+// the level under EXEC: no pick at all. The level's descendant sets are disjoint, so each dof K
+// of it takes its own FMA, y -= row[D] * y_K with y_K as the scalar operand, on its descendant
+// lanes: every lane still sees the one FMA of the select form with the same operands (the same bits),
+// and a level is n readlanes + n (EXEC write, FMA) in one statement
 template <int D>
+struct LevelSet {  // the level's dofs that have descendants
+    int dof[5];
+    int n;
+    constexpr LevelSet() : dof(), n(0) {
+        for (int j = kLevelStart[D]; j < kLevelStart[D + 1]; ++j)
+            if (kDescLo[kLevelDofs[j]] != 0 || kDescHi[kLevelDofs[j]] != 0) dof[n++] = kLevelDofs[j];
+    }
+};
+template <int D>
+struct LevelMasks {
+    static constexpr LevelSet<D> kSet{};
+    static constexpr int N = kSet.n;
+    static constexpr uint64_t lo(int q) { return kDescLo[kSet.dof[q]]; }
+    static constexpr uint64_t hi(int q) { return kDescHi[kSet.dof[q]]; }
+};
+template <int D>
+__device__ __forceinline__ void level_apply_exec(float a1, float a2, float& yl, float& y2) {
+    using G = LevelMasks<D>;
+    float l[G::N], k[G::N], s[G::N];
+    static_for<0, G::N, 1>([&](auto q) {
+        constexpr int K = G::kSet.dof[decltype(q)::value];
+        l[q] = a1;
+        k[q] = a2;
+        s[q] = K < 64 ? rdlane(yl, K) : rdlane(y2, K >= 64 ? K - 64 : 0);
+    });
+    fnma_lanes<G>(yl, y2, l, k, s);
+}
+// y <- L^-1 y by depth levels, shallowest first: the dofs of one level have disjoint descendant
+// sets, so a level is n readlanes + n selects + ONE fma with the row entry at that depth (the
+// select form, HE_EXEC_L = 0)
+template <int D, bool X = HE_EXEC_L != 0>
 __device__ __forceinline__ void solve_L_rows(const float (&r1)[kRowRegs], const float (&r2)[kRowRegs], float& yl,
                                              float& y2) {
     if constexpr (D < kNumLevels - 1) {
         constexpr uint64_t ulo = level_desc_lo<D>();
         constexpr uint64_t uhi = level_desc_hi<D>();
         if constexpr (ulo != 0 || uhi != 0) {
-            float t1, t2;  // written by level_pick on every lane of a set the level touches
-            undef_reg(t1);
-            undef_reg(t2);
-            level_pick<D, kLevelStart[D]>(yl, y2, t1, t2);
-            if constexpr (ulo != 0) yl = lanes<ulo>() ? yl - r1[D] * t1 : yl;
-            if constexpr (uhi != 0) y2 = lanes<uhi>() ? y2 - r2[D] * t2 : y2;
+            if constexpr (X) {
+                level_apply_exec<D>(r1[D], r2[D], yl, y2);
+            } else {
+                float t1, t2;  // written by level_pick on every lane of a set the level touches
+                undef_reg(t1);
+                undef_reg(t2);
+                level_pick<D, kLevelStart[D]>(yl, y2, t1, t2);
+                if constexpr (ulo != 0) yl = lanes<ulo>() ? yl - r1[D] * t1 : yl;
+                if constexpr (uhi != 0) y2 = lanes<uhi>() ? y2 - r2[D] * t2 : y2;
+            }
         }
-        solve_L_rows<D + 1>(r1, r2, yl, y2);
+        solve_L_rows<D + 1, X>(r1, r2, yl, y2);
     }
 }
 
@@ -307,7 +411,7 @@ __device__ __forceinline__ void solve_L_rows(const float (&r1)[kRowRegs], const 
 // compete with long-lived state for registers (the TGS iterations' velocity updates). p1 / p2: the
 // lane's rows of dof lane and dof 64 + lane (16-byte aligned, as load_rows); only entries below the
 // dof's depth are used, as in solve_L_rows.
-template <int D>
+template <int D, bool X>
 __device__ __forceinline__ void solve_L_stream(const f4v* p1, const f4v* p2, f4v c1, f4v c2, f4v n1, f4v n2, float& yl,
                                                float& y2) {
     if constexpr (D < kNumLevels - 1) {
@@ -324,20 +428,25 @@ __device__ __forceinline__ void solve_L_stream(const f4v* p1, const f4v* p2, f4v
         constexpr uint64_t ulo = level_desc_lo<D>();
         constexpr uint64_t uhi = level_desc_hi<D>();
         if constexpr (ulo != 0 || uhi != 0) {
-            float t1, t2;  // written by level_pick on every lane of a set the level touches
-            undef_reg(t1);
-            undef_reg(t2);
-            level_pick<D, kLevelStart[D]>(yl, y2, t1, t2);
-            if constexpr (ulo != 0) yl = lanes<ulo>() ? yl - c1[D % 4] * t1 : yl;
-            if constexpr (uhi != 0) y2 = lanes<uhi>() ? y2 - c2[D % 4] * t2 : y2;
+            if constexpr (X) {
+                level_apply_exec<D>(c1[D % 4], c2[D % 4], yl, y2);
+            } else {
+                float t1, t2;  // written by level_pick on every lane of a set the level touches
+                undef_reg(t1);
+                undef_reg(t2);
+                level_pick<D, kLevelStart[D]>(yl, y2, t1, t2);
+                if constexpr (ulo != 0) yl = lanes<ulo>() ? yl - c1[D % 4] * t1 : yl;
+                if constexpr (uhi != 0) y2 = lanes<uhi>() ? y2 - c2[D % 4] * t2 : y2;
+            }
         }
-        solve_L_stream<D + 1>(p1, p2, c1, c2, n1, n2, yl, y2);
+        solve_L_stream<D + 1, X>(p1, p2, c1, c2, n1, n2, yl, y2);
     }
 }
+template <bool X = HE_EXEC_L != 0>
 __device__ __forceinline__ void solve_L_streamed(const float* row1, const float* row2, float& yl, float& y2) {
     const f4v* p1 = reinterpret_cast<const f4v*>(row1);
     const f4v* p2 = reinterpret_cast<const f4v*>(row2);
-    solve_L_stream<0>(p1, p2, p1[0], p2[0], p1[1], p2[1], yl, y2);
+    solve_L_stream<0, X>(p1, p2, p1[0], p2[0], p1[1], p2[1], yl, y2);
 }
 
 // ---------------------------------------------------------------- y <- L^-T y, one vector
@@ -406,8 +515,8 @@ struct LTGroup {
 };
 // p1 = Lp + dj, p2 = Lp + dj2 (the lane's depth offsets, added once per group): each entry is one LDS
 // read at an immediate offset, no per-pivot address arithmetic. A lane that is not an ancestor of
-// K reads past row K (other rows of the factor, or the words after it); lt_group_apply's select
-// never lets that value in.
+// K reads past row K (other rows of the factor, or the words after it); the update never lets
+// that value in (its lane is outside the FMA's EXEC, or lt_group_apply's select drops it).
 template <int S0, int Q, int N>
 __device__ __forceinline__ void lt_group_load(const float* p1, const float* p2, float (&l1)[N], float (&l2)[N]) {
     if constexpr (Q < N) {
@@ -435,7 +544,29 @@ __device__ __forceinline__ void lt_group_apply(const float (&l1)[N], const float
         lt_group_apply<S0, Q + 1, N>(l1, l2, yk, yl, y2);
     }
 }
-template <int G>
+// the group's updates under EXEC, in the same order: one statement, each pivot's ancestor lanes
+// written to EXEC ahead of its FMA (HE_EXEC_LT; lt_group_apply is the select form)
+template <int S0, int N_>
+struct LTMasks {
+    static constexpr int N = N_;
+    static constexpr uint64_t lo(int q) {
+        const int K = kElimOrder[S0 + q];
+        if (kDofNanc[K] - 1 <= 0) return 0ull;
+        return K < 64 ? (kAncLo[K] & ~(1ull << (K & 63))) : kAncLo[K];
+    }
+    static constexpr uint64_t hi(int q) {
+        const int K = kElimOrder[S0 + q];
+        return K > 64 ? (uint64_t)(kAncHi[K] & ~(1u << (K - 64))) : 0ull;
+    }
+};
+template <int S0, int N>
+__device__ __forceinline__ void lt_group_apply_exec(const float (&l1)[N], const float (&l2)[N], const float (&yk)[N],
+                                                    float& yl, float& y2) {
+    using G = LTMasks<S0, N>;
+    // the root dof alone has no ancestor (a group of its own: it is everyone's ancestor)
+    if constexpr (N > 1 || G::lo(0) != 0) fnma_lanes<G>(yl, y2, l1, l2, yk);
+}
+template <int G, bool X>
 __device__ __forceinline__ void solve_LT_vec_pipe(const float* Lp, int dj, int dj2, float& yl, float& y2,
                                                   const float (&l1)[LTGroup<G>::N], const float (&l2)[LTGroup<G>::N]) {
     if constexpr (G < kLTPipeGroups.count) {
@@ -449,15 +580,17 @@ __device__ __forceinline__ void solve_LT_vec_pipe(const float* Lp, int dj, int d
         }
         float yk[C::N];
         lt_group_read<C::S0, 0, C::N>(yk, yl, y2);
-        lt_group_apply<C::S0, 0, C::N>(l1, l2, yk, yl, y2);
+        if constexpr (X) lt_group_apply_exec<C::S0, C::N>(l1, l2, yk, yl, y2);
+        else lt_group_apply<C::S0, 0, C::N>(l1, l2, yk, yl, y2);
         __builtin_amdgcn_sched_barrier(0);
-        solve_LT_vec_pipe<G + 1>(Lp, dj, dj2, yl, y2, n1, n2);
+        solve_LT_vec_pipe<G + 1, X>(Lp, dj, dj2, yl, y2, n1, n2);
     }
 }
+template <bool X = HE_EXEC_LT != 0>
 __device__ __forceinline__ void solve_LT_vec_pipelined(const float* Lp, int dj, int dj2, float& yl, float& y2) {
     float l1[LTGroup<0>::N], l2[LTGroup<0>::N];
     lt_group_load<LTGroup<0>::S0, 0, LTGroup<0>::N>(Lp + dj, Lp + dj2, l1, l2);
-    solve_LT_vec_pipe<0>(Lp, dj, dj2, yl, y2, l1, l2);
+    solve_LT_vec_pipe<0, X>(Lp, dj, dj2, yl, y2, l1, l2);
 }
 
 template <int K>

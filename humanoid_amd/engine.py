@@ -32,6 +32,7 @@ HE_SYMBOLS = (
     "he_refresh", "he_load_motions", "he_imitation_step", "he_motion_state", "he_reset_envs", "he_env_step",
     "he_imitation_reset_step", "he_set_debug_stamps", "he_hash_uniform", "he_ingest_clips", "he_set_eval",
     "he_set_amp", "he_amp_observations", "he_set_fused_step", "he_apply_body_forces", "he_apply_body_forces_at_pos",
+    "he_probe_masked_solves",
     # include/humanoid_rollout.h
     "he_rollout_store", "he_rollout_order", "he_rollout_gather", "he_gae", "he_gae_minibatch", "he_episode_step",
 )
@@ -79,6 +80,7 @@ def load_library(path: Optional[str] = None):
         "he_episode_step": [C.c_int32] + [V] * 14,
     }
     sigs.update(_abi.FORCE_PROTOTYPES)
+    sigs.update(_abi.PROBE_PROTOTYPES)
     for name, args in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = args

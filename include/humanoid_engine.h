@@ -414,6 +414,13 @@ int he_amp_observations(int k, const float* root_pos, const float* root_rot, con
  * library returns nonzero for a non-NULL buffer. */
 int he_set_debug_stamps(he_engine* h, uint64_t* device_buffer);
 
+/* Test probe of the physics kernel's joint-space vector solves on the SMPL dof tree, without an
+ * engine: factor [1256] is a packed unit-lower factor L in the kernel's layout (row K of L at
+ * offset pack_start[K], its entry for the ancestor at tree depth d at pack_start[K] + d), y [n][75]
+ * the vectors, one wave each. out [4][n][75]: L^-T y with the lane-masked updates run under EXEC,
+ * L^-T y with them as FMA + select, then L^-1 y in the same two forms (device pointers). */
+int he_probe_masked_solves(const float* factor, const float* y, int n, float* out, void* stream);
+
 /* hash-based uniform used by he_env_step (exposed for parity tests): out[k] for env ids[k]. */
 float he_hash_uniform(uint64_t seed, uint64_t step_index, uint32_t env);
 
