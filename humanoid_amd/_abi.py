@@ -1,7 +1,8 @@
 """ctypes mirrors of ``include/humanoid_engine.h`` and helpers to fill them.
 
 Pure data-contract code: the product shim (``engine.py``) and the test-side oracle wrapper
-(``oracle/oracle.py``) both use these layouts.
+(``oracle/oracle.py``) both use these layouts. The three bindings (``engine.py``, ``render.py``,
+``dynamics.py``) also share the library loader and the tensor check here.
 """
 import ctypes as C
 
@@ -52,6 +53,50 @@ FORCE_PROTOTYPES = {
 PROBE_PROTOTYPES = {
     "he_probe_masked_solves": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
 }
+
+
+def bind_library(path, prototypes):
+    """Load the C-ABI library at ``path`` and bind ``prototypes``: name -> argument types for a
+    function that returns the int status code, or (return type, argument types) for any other. The
+    table is the one statement of what a binding calls: its keys are the library's exported symbols."""
+    lib = C.CDLL(path)
+    for name, proto in prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = proto if isinstance(proto, tuple) else (C.c_int, proto)
+    return lib
+
+
+def destroy_handle(obj, destroy):
+    """The ``__del__`` of a binding object: its handle ``obj.h`` goes to the library's ``destroy`` once.
+    Never raises (the interpreter may be shutting down)."""
+    try:
+        if getattr(obj, "h", None) and obj.lib is not None:
+            getattr(obj.lib, destroy)(obj.h)
+            obj.h = None
+    except Exception:
+        pass
+
+
+def check_tensor(t, dtype, shape, device, what, error_cls, at_least=None):
+    """The check every tensor passes before its pointer is handed to a library: a contiguous torch
+    tensor of this dtype on this device, and of this ``shape`` (a tuple), of this many elements (an
+    int) or, with ``shape`` None, of ``at_least`` that many elements when given; else ``error_cls``
+    naming ``what``. Returns the device pointer."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise error_cls(f"{what}: expected a torch tensor, got {type(t).__name__}")
+    if shape is None:
+        size_ok = at_least is None or t.numel() >= at_least
+        want = "tensor" if at_least is None else f"tensor of at least {at_least} elements"
+    elif isinstance(shape, int):
+        size_ok, want = t.numel() == shape, f"tensor of {shape} elements"
+    else:
+        size_ok, want = tuple(t.shape) == tuple(shape), f"{tuple(shape)}"
+    if t.device != device or t.dtype != dtype or not t.is_contiguous() or not size_ok:
+        raise error_cls(f"{what}: expected contiguous {dtype} {want} on {device}, got "
+                        f"{'contiguous' if t.is_contiguous() else 'non-contiguous'} {t.dtype} {tuple(t.shape)} "
+                        f"on {t.device}")
+    return C.c_void_p(t.data_ptr())
 
 
 class HeModel(C.Structure):

@@ -18,12 +18,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
+#include <memory>
 
 #include "../../include/humanoid_dynamics.h"
+#include "he_host.h"
 #include "he_topo.h"
 
 namespace {
@@ -344,58 +343,26 @@ __global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
     }
 }
 
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-#define HD_CHECK(expr)                                                                   \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(_e));       \
-    } while (0)
-
 }  // namespace
 
 struct hd_dynamics {
     int device = 0;
     int num_envs = 0;
-    DModel* d_model = nullptr;
+    DeviceArray<DModel> d_model;
 };
 
 extern "C" {
 
-const char* hd_last_error(void) { return g_err.c_str(); }
+const char* hd_last_error(void) { return last_error(); }
 int hd_version(void) { return 1; }
 
 int hd_validate_model(const he_model* model) {
-    if (!model) return fail("model: null model");
-    if (model->num_bodies != NB || model->num_dof != ND)
-        return fail("model: the kernel is built for %d bodies / %d dofs (got %d / %d)", NB, ND, model->num_bodies,
-                    model->num_dof);
-    if (model->num_pairs < 0 || model->num_pairs > HE_MAX_PAIRS) return fail("model: bad pair count %d", model->num_pairs);
-    if (model->parents[0] != -1) return fail("model: body 0 must be the root");
-    int depth[NB] = {0};
+    if (check_model(model, "model", HE_MAX_BOXES)) return 1;
+    int depth[NB] = {0};  // this kernel's own bound: one pass per tree level
     for (int b = 1; b < NB; ++b) {
-        if (model->parents[b] < 0 || model->parents[b] >= b) return fail("model: bodies must be in DFS order");
         depth[b] = depth[model->parents[b]] + 1;
         if (depth[b] > kMaxDepth) return fail("model: body %d is %d joints from the root, at most %d", b, depth[b], kMaxDepth);
     }
-    int boxes = 0;
-    for (int b = 0; b < NB; ++b) {
-        const int32_t t = model->geom_type[b];
-        if (t != HE_GEOM_SPHERE && t != HE_GEOM_CAPSULE && t != HE_GEOM_BOX)
-            return fail("model: body %d has geom type %d (sphere 0, capsule 1, box 2)", b, t);
-        boxes += t == HE_GEOM_BOX;
-    }
-    if (boxes > HE_MAX_BOXES) return fail("model: %d box geoms, the engine holds at most %d", boxes, HE_MAX_BOXES);
     return 0;
 }
 
@@ -421,27 +388,18 @@ int hd_create(int device, const he_model* model, const float gravity[3], int num
             if (dm.anc[d] >> b & 1u) dm.sub[b] |= 1u << d;
     for (int d = 0; d < ND; ++d) dm.armature[d] = model->armature[d];
     for (int c = 0; c < 3; ++c) dm.gravity[c] = gravity[c];
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail("hd_create: no HIP device visible (there is no CPU path)");
-    if (device < 0 || device >= count) return fail("hd_create: device %d of %d", device, count);
-    HD_CHECK(hipSetDevice(device));
-    hd_dynamics* h = new hd_dynamics;
+    if (select_device(device, "hd_create")) return 1;
+    std::unique_ptr<hd_dynamics> h(new hd_dynamics);  // a failed step below frees it and its array
     h->device = device;
     h->num_envs = num_envs;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_model), sizeof(DModel));
-    if (e == hipSuccess) e = hipMemcpy(h->d_model, &dm, sizeof(DModel), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hd_destroy(h);
-        return fail("hd_create: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    HE_CHECK(h->d_model.assign(&dm, 1));
+    *out = h.release();
     return 0;
 }
 
 int hd_destroy(hd_dynamics* h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
-    if (h->d_model) (void)hipFree(h->d_model);
     delete h;
     return 0;
 }
@@ -465,7 +423,7 @@ int hd_compute(hd_dynamics* h, const float* root_state, const float* dof_state, 
     P.bias = bias_out;
     P.flags = flags;
     hipLaunchKernelGGL(dynamics_kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
-    HD_CHECK(hipGetLastError());
+    HE_CHECK(hipGetLastError());
     return 0;
 }
 

@@ -1,38 +1,21 @@
 // he_engine.cpp -- C-ABI implementation of libhumanoid_engine.so (include/humanoid_engine.h).
-// Owns the device state (hipMalloc), the device model/topology blobs and the device motion
-// library, and launches the gfx950 kernels on the caller's stream. No host synchronisation on
-// any compute entry point; allocation happens only in he_create_envs / he_load_motions.
+// Owns the device state (he_host.h DeviceArray members), the device model/topology blobs and the
+// device motion library, and launches the gfx950 kernels on the caller's stream. No host
+// synchronisation on any compute entry point; allocation happens only in the he_set_* / he_create_envs
+// / he_load_motions / he_ingest_clips calls, which change the engine only after their last step.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdlib>
-#include <cstdio>
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/humanoid_engine.h"
+#include "he_host.h"
 #include "he_kernels.h"
 #include "he_topo.h"
-
-size_t physics_lds_bytes();
-
-namespace {
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-}  // namespace
 
 // error text for the other C-ABI translation units (he_rollout.hip)
 int he_fail_text(const char* text) {
@@ -40,56 +23,59 @@ int he_fail_text(const char* text) {
     return 1;
 }
 
-namespace {
-#define HE_CHECK(expr)                                                                         \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) return fail("%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+// the device motion library (he_load_motions / he_ingest_clips build one and move it into the engine)
+struct MotionTables {
+    DeviceArray<float> hot, cold, lengths, dt;
+    DeviceArray<int64_t> starts, nframes;
+    int count = 0;  // motions; 0: nothing loaded
+};
 
-template <typename T>
-hipError_t dalloc(T** p, size_t n) {
-    return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T) > 0 ? n * sizeof(T) : 16);
+// the tables of M motions over F frames: the frame records allocated, the per-motion arrays filled
+static int stage_motion_tables(MotionTables& t, int64_t F, int M, const float* lengths, const float* dt,
+                               const int64_t* starts, const int64_t* nframes) {
+    HE_CHECK(t.hot.alloc((size_t)F * HE_NUM_BODIES * HE_MOTION_HOT));
+    HE_CHECK(t.cold.alloc((size_t)F * HE_NUM_BODIES * HE_MOTION_COLD));
+    HE_CHECK(t.lengths.assign(lengths, M));
+    HE_CHECK(t.dt.assign(dt, M));
+    HE_CHECK(t.starts.assign(starts, M));
+    HE_CHECK(t.nframes.assign(nframes, M));
+    t.count = M;
+    return 0;
 }
-}  // namespace
 
 struct he_engine {
     int device = 0;
     he_sim_params params{};
     he_model model{};
     bool has_model = false;
-    he_model* d_model = nullptr;
-    PhysTopo* d_topo = nullptr;
+    DeviceArray<he_model> d_model;
+    DeviceArray<PhysTopo> d_topo;
+    DeviceArray<float> d_rest;      // [24,3] zero-pose body origins in the root frame
     int num_envs = 0;
-    float *root = nullptr, *dof_state = nullptr, *rb = nullptr, *cf = nullptr, *dof_force = nullptr, *targets = nullptr;
-    int32_t* num_contacts = nullptr;
-    int32_t* dropped = nullptr;
-    float* cache = nullptr;
-    float* init_root = nullptr;     // [N,13] HE_BUF_INIT_ROOT_STATE
-    int32_t* meta_cache = nullptr;  // [N,8] the imitation kernel's per-env motion-metadata cache
-    float* d_rest = nullptr;        // [24,3] zero-pose body origins in the root frame
+    // the per-env buffers; env_buffers() below states their shapes, types and initial contents
+    DeviceArray<float> root, dof_state, rb, cf, dof_force, targets, cache;
+    DeviceArray<int32_t> num_contacts, dropped;
+    DeviceArray<float> init_root;
+    DeviceArray<int32_t> meta_cache;  // the imitation kernel's per-env motion-metadata cache
     bool component_limits = false;  // a dof bound inside (-pi + guard, pi - guard): not implemented
     int fused_step = -1;            // he_env_step as one launch: 1 / 0 (he_set_fused_step), -1 auto
+    // borrowed from the caller (he_set_env_properties), who keeps them alive
     const float *mass_scale = nullptr, *friction = nullptr;
     const int32_t* terrain_kind = nullptr;
-    float *pd_offset = nullptr, *pd_scale = nullptr;
-    int32_t* frozen = nullptr;
+    DeviceArray<float> pd_offset, pd_scale;
+    DeviceArray<int32_t> frozen;
     int clip_actions = 1;
     bool has_pd = false;
-    he_eval_buffers eval{};
+    he_eval_buffers eval{};  // borrowed device pointers (he_set_eval)
     int has_eval = 0;
-    he_amp_buffers amp{};
+    he_amp_buffers amp{};    // borrowed device pointers (he_set_amp)
     int has_amp = 0;
-    // motion library
-    float *m_hot = nullptr, *m_cold = nullptr, *m_lengths = nullptr, *m_dt = nullptr;
-    int64_t *m_starts = nullptr, *m_nframes = nullptr;
-    int64_t m_frames = 0;
-    int m_motions = 0;
-    unsigned long long* stamps = nullptr;
+    MotionTables motions;
+    unsigned long long* stamps = nullptr;  // borrowed (he_set_debug_stamps)
     // the physics launch's dispatch order (he_kernels.h launch_physics_order), rebuilt from the envs'
     // cycle counts every order_every launches; HE_PHYS_ORDER=0 keeps workgroup id = env
-    int32_t* order = nullptr;    // [N]
-    uint32_t* cost = nullptr;    // [N]
+    DeviceArray<int32_t> order;
+    DeviceArray<uint32_t> cost;
     int order_every = 8;
     long long launches = 0;
     // HE_TGS_LEGS=0 in the environment: no leg class (physics_kernel_tgs's Zh products over every dof
@@ -102,16 +88,52 @@ struct he_engine {
     long long order_seq = 0;          // rebuilds issued
     long long order_seen_seq = -1;    // the rebuild the last physics launch waited for, on ...
     hipStream_t order_seen_stream = nullptr;  // ... this stream
-    // external wrenches (he_apply_body_forces): the [N,24,6] world-axis (torque, force at the CoM) rows
+    // external wrenches (he_apply_body_forces): the world-axis (torque, force at the CoM) rows
     // and the gym.simulate() calls they still act in (0: nothing pending; the rows are then overwritten
     // by the next call, not accumulated into)
-    float* wrench = nullptr;
+    DeviceArray<float> wrench;
     int wrench_hold = 0;
+
+    ~he_engine() {
+        if (order_ready) (void)hipEventDestroy(order_ready);
+    }
 };
+
+namespace {
+// A per-env buffer of the engine: what he_get_buffer calls it (-1: internal), its array, rows per env,
+// columns (0: one-dimensional), element type and the byte every element starts as. The table drives
+// he_create_envs and he_get_buffer; a new buffer is a member of he_engine and a row here.
+struct EnvBuffer {
+    int kind;
+    DeviceBytes* mem;
+    int rows, cols, dtype, fill;
+    size_t bytes(int N) const { return (size_t)N * rows * (cols ? cols : 1) * 4; }  // both dtypes: 4 bytes
+};
+
+std::vector<EnvBuffer> env_buffers(he_engine* h) {
+    const int F32 = HE_DTYPE_F32, I32 = HE_DTYPE_I32, NB = HE_NUM_BODIES, ND = HE_NUM_DOF;
+    return {
+        {HE_BUF_ROOT_STATE, &h->root, 1, 13, F32, 0},
+        {HE_BUF_DOF_STATE, &h->dof_state, ND, 2, F32, 0},
+        {HE_BUF_RB_STATE, &h->rb, NB, 13, F32, 0},
+        {HE_BUF_CONTACT_FORCE, &h->cf, NB, 3, F32, 0},
+        {HE_BUF_DOF_FORCE, &h->dof_force, ND, 0, F32, 0},
+        {HE_BUF_DOF_TARGET, &h->targets, 1, ND, F32, 0},
+        {HE_BUF_NUM_CONTACTS, &h->num_contacts, 1, 0, I32, 0},
+        {HE_BUF_DROPPED_CONTACTS, &h->dropped, 1, 0, I32, 0},
+        {HE_BUF_CONTACT_CACHE, &h->cache, 1, HE_CACHE_WORDS, F32, 0},
+        {HE_BUF_INIT_ROOT_STATE, &h->init_root, 1, 13, F32, 0},
+        {HE_BUF_PHYS_ORDER, &h->order, 1, 0, I32, 0},
+        {HE_BUF_PHYS_COST, &h->cost, 1, 0, I32, 0},
+        {-1, &h->meta_cache, 1, 8, I32, 0xFF},  // motion -1: empty
+        {-1, &h->wrench, NB, 6, F32, 0},
+    };
+}
+}  // namespace
 
 extern "C" {
 
-const char* he_last_error(void) { return g_err.c_str(); }
+const char* he_last_error(void) { return last_error(); }
 int he_version(void) { return 1; }
 
 int he_device_count(int* count) {
@@ -121,9 +143,7 @@ int he_device_count(int* count) {
 
 int he_create(const he_sim_params* params, int device, he_engine** out) {
     if (!params || !out) return fail("he_create: null argument");
-    int n = 0;
-    HE_CHECK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) return fail("he_create: device %d out of range (%d devices)", device, n);
+    if (select_device(device, "he_create")) return 1;
     hipDeviceProp_t prop;
     HE_CHECK(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
@@ -149,64 +169,44 @@ int he_create(const he_sim_params* params, int device, he_engine** out) {
 
 int he_set_model(he_engine* h, const he_model* model) {
     if (!h || !model) return fail("he_set_model: null argument");
-    if (model->num_bodies != HE_NUM_BODIES || model->num_dof != HE_NUM_DOF)
-        return fail("he_set_model: engine is built for %d bodies / %d dofs (got %d / %d)", HE_NUM_BODIES, HE_NUM_DOF,
-                    model->num_bodies, model->num_dof);
-    if (model->num_pairs < 0 || model->num_pairs > HE_MAX_PAIRS) return fail("he_set_model: bad pair count");
-    if (model->parents[0] != -1) return fail("he_set_model: body 0 must be the root");
-    for (int b = 1; b < HE_NUM_BODIES; ++b)
-        if (model->parents[b] < 0 || model->parents[b] >= b) return fail("he_set_model: bodies must be in DFS order");
-    for (int b = 0; b < HE_NUM_BODIES; ++b)
-        if (model->geom_type[b] != HE_GEOM_SPHERE && model->geom_type[b] != HE_GEOM_CAPSULE && model->geom_type[b] != HE_GEOM_BOX)
-            return fail("he_set_model: body %d has geom type %d (sphere 0, capsule 1, box 2)", b, model->geom_type[b]);
-    // every check before the engine changes: a refused model leaves the previous one in place
+    if (check_model(model, "he_set_model", HE_MAX_BOXES)) return 1;
     PhysTopo topo{};
     he_build_topo(*model, topo);
     if (topo.nnz > HE_NNZ_MAX) return fail("he_set_model: mass-matrix pattern too large (%d)", topo.nnz);
-    if (topo.num_boxes > HE_MAX_BOXES)
-        return fail("he_set_model: %d box geoms (the kernel's corner lanes hold at most %d)", topo.num_boxes, HE_MAX_BOXES);
+    // the zero pose's body origins in the root frame: every local rotation is the identity, so the
+    // joint offsets add up along the chain (the Default state init's rigid-body rows)
+    float rest[HE_NUM_BODIES][3] = {};
+    for (int b = 1; b < HE_NUM_BODIES; ++b)
+        for (int c = 0; c < 3; ++c) rest[b][c] = rest[model->parents[b]][c] + model->local_pos[b][c];
+    // the device copies in locals first: a refused or failed call leaves the previous model in place
     HE_CHECK(hipSetDevice(h->device));
+    DeviceArray<he_model> d_model;
+    DeviceArray<PhysTopo> d_topo;
+    DeviceArray<float> d_rest;
+    HE_CHECK(d_model.assign(model, 1));
+    HE_CHECK(d_topo.assign(&topo, 1));
+    HE_CHECK(d_rest.assign(&rest[0][0], HE_NUM_BODIES * 3));
+    h->d_model = std::move(d_model);
+    h->d_topo = std::move(d_topo);
+    h->d_rest = std::move(d_rest);
     h->model = *model;
     // the kernel holds every joint's rotation angle below pi - 0.02 (the exp-map branch cut); dof
     // bounds inside that band would need per-component rows (the oracle has them, the kernel not)
     h->component_limits = false;
     for (int d = 0; d < HE_NUM_DOF; ++d)
         if (std::fabs(model->dof_lower[d]) < 3.1215f || std::fabs(model->dof_upper[d]) < 3.1215f) h->component_limits = true;
-    if (!h->d_model) HE_CHECK(dalloc(&h->d_model, 1));
-    if (!h->d_topo) HE_CHECK(dalloc(&h->d_topo, 1));
-    HE_CHECK(hipMemcpy(h->d_model, model, sizeof(he_model), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->d_topo, &topo, sizeof(PhysTopo), hipMemcpyHostToDevice));
-    // the zero pose's body origins in the root frame: every local rotation is the identity, so the
-    // joint offsets add up along the chain (the Default state init's rigid-body rows)
-    float rest[HE_NUM_BODIES][3] = {};
-    for (int b = 1; b < HE_NUM_BODIES; ++b)
-        for (int c = 0; c < 3; ++c) rest[b][c] = rest[model->parents[b]][c] + model->local_pos[b][c];
-    if (!h->d_rest) HE_CHECK(dalloc(&h->d_rest, HE_NUM_BODIES * 3));
-    HE_CHECK(hipMemcpy(h->d_rest, rest, sizeof(rest), hipMemcpyHostToDevice));
     h->has_model = true;
     return 0;
 }
 
 static int warm_kernels(int device);
 
-int he_create_envs(he_engine* h, int num_envs, const float* host_start_xy) {
-    if (!h) return fail("he_create_envs: null handle");
-    if (!h->has_model) return fail("he_create_envs: call he_set_model first");
-    if (num_envs <= 0) return fail("he_create_envs: num_envs must be positive");
-    if (h->num_envs) return fail("he_create_envs: envs already created");
-    HE_CHECK(hipSetDevice(h->device));
-    // before any allocation: a failed warm-up leaves nothing behind to leak or re-allocate
-    if (warm_kernels(h->device)) return 1;
-    const int N = num_envs;
-    HE_CHECK(dalloc(&h->root, (size_t)N * 13));
-    HE_CHECK(dalloc(&h->dof_state, (size_t)N * HE_NUM_DOF * 2));
-    HE_CHECK(dalloc(&h->rb, (size_t)N * HE_NUM_BODIES * 13));
-    HE_CHECK(dalloc(&h->cf, (size_t)N * HE_NUM_BODIES * 3));
-    HE_CHECK(dalloc(&h->dof_force, (size_t)N * HE_NUM_DOF));
-    HE_CHECK(dalloc(&h->targets, (size_t)N * HE_NUM_DOF));
-    HE_CHECK(dalloc(&h->num_contacts, (size_t)N));
-    HE_CHECK(dalloc(&h->dropped, (size_t)N));
-    HE_CHECK(dalloc(&h->cache, (size_t)N * HE_CACHE_WORDS));
+// allocates and initialises every per-env buffer; the caller releases them all when this fails
+static int init_env_buffers(he_engine* h, int N, const float* host_start_xy) {
+    for (const EnvBuffer& b : env_buffers(h)) {
+        HE_CHECK(b.mem->alloc(b.bytes(N)));
+        HE_CHECK(b.mem->fill(b.fill, b.bytes(N)));
+    }
     // humanoid_phc.py:340-347: start pose (x, y) + z 0.89, identity rotation, zero velocity
     std::vector<float> root((size_t)N * 13, 0.f);
     for (int e = 0; e < N; ++e) {
@@ -216,44 +216,37 @@ int he_create_envs(he_engine* h, int num_envs, const float* host_start_xy) {
         r[2] = 0.89f;
         r[6] = 1.f;
     }
-    HE_CHECK(hipMemcpy(h->root, root.data(), root.size() * sizeof(float), hipMemcpyHostToDevice));
+    HE_CHECK(h->root.upload(root.data(), root.size()));
     // _initial_humanoid_root_states (humanoid_phc.py:522-523): the creation poses, zero velocities
-    HE_CHECK(dalloc(&h->init_root, (size_t)N * 13));
-    HE_CHECK(hipMemcpy(h->init_root, root.data(), root.size() * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemset(h->dof_state, 0, (size_t)N * HE_NUM_DOF * 2 * sizeof(float)));
-    HE_CHECK(hipMemset(h->rb, 0, (size_t)N * HE_NUM_BODIES * 13 * sizeof(float)));
-    HE_CHECK(hipMemset(h->cf, 0, (size_t)N * HE_NUM_BODIES * 3 * sizeof(float)));
-    HE_CHECK(hipMemset(h->dof_force, 0, (size_t)N * HE_NUM_DOF * sizeof(float)));
-    HE_CHECK(hipMemset(h->targets, 0, (size_t)N * HE_NUM_DOF * sizeof(float)));
-    HE_CHECK(hipMemset(h->num_contacts, 0, (size_t)N * sizeof(int32_t)));
-    HE_CHECK(hipMemset(h->dropped, 0, (size_t)N * sizeof(int32_t)));
-    HE_CHECK(hipMemset(h->cache, 0, (size_t)N * HE_CACHE_WORDS * sizeof(float)));
-    HE_CHECK(dalloc(&h->meta_cache, (size_t)N * 8));
-    HE_CHECK(hipMemset(h->meta_cache, 0xFF, (size_t)N * 8 * sizeof(int32_t)));  // motion -1: empty
+    HE_CHECK(h->init_root.upload(root.data(), root.size()));
     // dispatch order: the identity until the first rebuild
     std::vector<int32_t> ord((size_t)N);
     for (int e = 0; e < N; ++e) ord[e] = e;
-    HE_CHECK(dalloc(&h->order, (size_t)N));
-    HE_CHECK(hipMemcpy(h->order, ord.data(), ord.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HE_CHECK(dalloc(&h->cost, (size_t)N));
-    HE_CHECK(hipMemset(h->cost, 0, (size_t)N * sizeof(uint32_t)));
-    HE_CHECK(dalloc(&h->wrench, (size_t)N * HE_NUM_BODIES * 6));
-    HE_CHECK(hipMemset(h->wrench, 0, (size_t)N * HE_NUM_BODIES * 6 * sizeof(float)));
+    HE_CHECK(h->order.upload(ord.data(), ord.size()));
+    return 0;
+}
+
+int he_create_envs(he_engine* h, int num_envs, const float* host_start_xy) {
+    if (!h) return fail("he_create_envs: null handle");
+    if (!h->has_model) return fail("he_create_envs: call he_set_model first");
+    if (num_envs <= 0) return fail("he_create_envs: num_envs must be positive");
+    if (h->num_envs) return fail("he_create_envs: envs already created");
+    HE_CHECK(hipSetDevice(h->device));
+    // before any allocation: a failed warm-up leaves nothing behind to leak or re-allocate
+    if (warm_kernels(h->device)) return 1;
+    if (init_env_buffers(h, num_envs, host_start_xy)) {
+        for (const EnvBuffer& b : env_buffers(h)) b.mem->release();  // as before the call: a retry is valid
+        return 1;
+    }
     if (const char* v = std::getenv("HE_PHYS_ORDER")) h->order_every = std::atoi(v);
     if (const char* v = std::getenv("HE_TGS_LEGS")) h->full_dofs = std::atoi(v) == 0;
-    h->num_envs = N;
+    h->num_envs = num_envs;
     return 0;
 }
 
 int he_destroy(he_engine* h) {
     if (!h) return 0;
-    hipSetDevice(h->device);
-    void* ptrs[] = {h->d_model, h->d_topo, h->root, h->dof_state, h->rb, h->cf, h->dof_force, h->targets,
-                    h->num_contacts, h->dropped, h->cache, h->init_root, h->meta_cache, h->d_rest, h->pd_offset, h->pd_scale, h->frozen, h->m_hot, h->m_cold, h->m_lengths,
-                    h->m_dt, h->m_starts, h->m_nframes, h->order, h->cost, h->wrench};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    if (h->order_ready) hipEventDestroy(h->order_ready);
+    (void)hipSetDevice(h->device);
     delete h;
     return 0;
 }
@@ -261,24 +254,16 @@ int he_destroy(he_engine* h) {
 int he_get_buffer(he_engine* h, int kind, void** dptr, int64_t* shape, int* ndim, int* dtype) {
     if (!h || !dptr || !shape || !ndim || !dtype) return fail("he_get_buffer: null argument");
     if (!h->num_envs) return fail("he_get_buffer: no envs created");
-    const int64_t N = h->num_envs;
-    *dtype = HE_DTYPE_F32;
-    switch (kind) {
-        case HE_BUF_ROOT_STATE: *dptr = h->root; *ndim = 2; shape[0] = N; shape[1] = 13; break;
-        case HE_BUF_DOF_STATE: *dptr = h->dof_state; *ndim = 2; shape[0] = N * HE_NUM_DOF; shape[1] = 2; break;
-        case HE_BUF_RB_STATE: *dptr = h->rb; *ndim = 2; shape[0] = N * HE_NUM_BODIES; shape[1] = 13; break;
-        case HE_BUF_CONTACT_FORCE: *dptr = h->cf; *ndim = 2; shape[0] = N * HE_NUM_BODIES; shape[1] = 3; break;
-        case HE_BUF_DOF_FORCE: *dptr = h->dof_force; *ndim = 1; shape[0] = N * HE_NUM_DOF; break;
-        case HE_BUF_DOF_TARGET: *dptr = h->targets; *ndim = 2; shape[0] = N; shape[1] = HE_NUM_DOF; break;
-        case HE_BUF_NUM_CONTACTS: *dptr = h->num_contacts; *ndim = 1; shape[0] = N; *dtype = HE_DTYPE_I32; break;
-        case HE_BUF_DROPPED_CONTACTS: *dptr = h->dropped; *ndim = 1; shape[0] = N; *dtype = HE_DTYPE_I32; break;
-        case HE_BUF_CONTACT_CACHE: *dptr = h->cache; *ndim = 2; shape[0] = N; shape[1] = HE_CACHE_WORDS; break;
-        case HE_BUF_INIT_ROOT_STATE: *dptr = h->init_root; *ndim = 2; shape[0] = N; shape[1] = 13; break;
-        case HE_BUF_PHYS_ORDER: *dptr = h->order; *ndim = 1; shape[0] = N; *dtype = HE_DTYPE_I32; break;
-        case HE_BUF_PHYS_COST: *dptr = h->cost; *ndim = 1; shape[0] = N; *dtype = HE_DTYPE_I32; break;
-        default: return fail("he_get_buffer: unknown buffer kind %d", kind);
+    for (const EnvBuffer& b : env_buffers(h)) {
+        if (b.kind != kind || kind < 0) continue;
+        *dptr = b.mem->get();
+        *dtype = b.dtype;
+        *ndim = b.cols ? 2 : 1;
+        shape[0] = (int64_t)h->num_envs * b.rows;
+        if (b.cols) shape[1] = b.cols;
+        return 0;
     }
-    return 0;
+    return fail("he_get_buffer: unknown buffer kind %d", kind);
 }
 
 int he_set_dof_targets(he_engine* h, const float* src, void* stream) {
@@ -364,14 +349,16 @@ int he_set_pd_params(he_engine* h, const float* host_offset, const float* host_s
                      int clip_actions) {
     if (!h || !host_offset || !host_scale) return fail("he_set_pd_params: null argument");
     HE_CHECK(hipSetDevice(h->device));
-    if (!h->pd_offset) HE_CHECK(dalloc(&h->pd_offset, HE_NUM_DOF));
-    if (!h->pd_scale) HE_CHECK(dalloc(&h->pd_scale, HE_NUM_DOF));
-    if (!h->frozen) HE_CHECK(dalloc(&h->frozen, HE_NUM_DOF));
     std::vector<int32_t> fz(HE_NUM_DOF, 0);
     if (host_frozen_mask) std::memcpy(fz.data(), host_frozen_mask, sizeof(int32_t) * HE_NUM_DOF);
-    HE_CHECK(hipMemcpy(h->pd_offset, host_offset, sizeof(float) * HE_NUM_DOF, hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->pd_scale, host_scale, sizeof(float) * HE_NUM_DOF, hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->frozen, fz.data(), sizeof(int32_t) * HE_NUM_DOF, hipMemcpyHostToDevice));
+    DeviceArray<float> offset, scale;
+    DeviceArray<int32_t> frozen;
+    HE_CHECK(offset.assign(host_offset, HE_NUM_DOF));
+    HE_CHECK(scale.assign(host_scale, HE_NUM_DOF));
+    HE_CHECK(frozen.assign(fz.data(), HE_NUM_DOF));
+    h->pd_offset = std::move(offset);
+    h->pd_scale = std::move(scale);
+    h->frozen = std::move(frozen);
     h->clip_actions = clip_actions;
     h->has_pd = true;
     return 0;
@@ -500,8 +487,8 @@ int he_refresh(he_engine* h, void* stream) {
 
 // new motion tables: the imitation kernel's per-env metadata cache (keyed by motion id) is stale
 static hipError_t invalidate_meta_cache(he_engine* h) {
-    if (!h->meta_cache) return hipSuccess;
-    return hipMemset(h->meta_cache, 0xFF, (size_t)h->num_envs * 8 * sizeof(int32_t));
+    if (!h->num_envs) return hipSuccess;
+    return h->meta_cache.fill(0xFF, (size_t)h->num_envs * 8);
 }
 
 int he_load_motions(he_engine* h, int64_t F, int M, const float* gts, const float* grs, const float* lrs,
@@ -534,24 +521,13 @@ int he_load_motions(he_engine* h, int64_t F, int M, const float* gts, const floa
                 c[4] = dvs[d3]; c[5] = dvs[d3 + 1]; c[6] = dvs[d3 + 2];
             }
         }
-    void* old[] = {h->m_hot, h->m_cold, h->m_lengths, h->m_dt, h->m_starts, h->m_nframes};
-    for (void* p : old)
-        if (p) HE_CHECK(hipFree(p));
-    HE_CHECK(dalloc(&h->m_hot, hot.size()));
-    HE_CHECK(dalloc(&h->m_cold, cold.size()));
-    HE_CHECK(dalloc(&h->m_lengths, (size_t)M));
-    HE_CHECK(dalloc(&h->m_dt, (size_t)M));
-    HE_CHECK(dalloc(&h->m_starts, (size_t)M));
-    HE_CHECK(dalloc(&h->m_nframes, (size_t)M));
-    HE_CHECK(hipMemcpy(h->m_hot, hot.data(), hot.size() * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_cold, cold.data(), cold.size() * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_lengths, lengths, M * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_dt, dt, M * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_starts, length_starts, M * sizeof(int64_t), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_nframes, num_frames, M * sizeof(int64_t), hipMemcpyHostToDevice));
-    h->m_frames = F;
-    h->m_motions = M;
+    // the new tables in a local: a failure frees them and leaves the loaded library in place
+    MotionTables t;
+    if (stage_motion_tables(t, F, M, lengths, dt, length_starts, num_frames)) return 1;
+    HE_CHECK(t.hot.upload(hot.data(), hot.size()));
+    HE_CHECK(t.cold.upload(cold.data(), cold.size()));
     HE_CHECK(invalidate_meta_cache(h));
+    h->motions = std::move(t);
     return 0;
 }
 
@@ -591,53 +567,36 @@ int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames,
     HE_CHECK(hipSetDevice(h->device));
     const hipStream_t st = (hipStream_t)stream;
     HE_CHECK(hipStreamSynchronize(st));  // tables may be in use by queued kernels
-    void* old[] = {h->m_hot, h->m_cold, h->m_lengths, h->m_dt, h->m_starts, h->m_nframes};
-    for (void* p : old)
-        if (p) HE_CHECK(hipFree(p));
-    h->m_hot = h->m_cold = h->m_lengths = h->m_dt = nullptr;
-    h->m_starts = h->m_nframes = nullptr;
-    h->m_motions = 0;
-    const int B = HE_NUM_BODIES;
-    HE_CHECK(dalloc(&h->m_hot, (size_t)F * B * HE_MOTION_HOT));
-    HE_CHECK(dalloc(&h->m_cold, (size_t)F * B * HE_MOTION_COLD));
-    HE_CHECK(dalloc(&h->m_lengths, (size_t)num_motions));
-    HE_CHECK(dalloc(&h->m_dt, (size_t)num_motions));
-    HE_CHECK(dalloc(&h->m_starts, (size_t)num_motions));
-    HE_CHECK(dalloc(&h->m_nframes, (size_t)num_motions));
-    HE_CHECK(hipMemcpy(h->m_lengths, ml.data(), num_motions * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_dt, mdt.data(), num_motions * sizeof(float), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_starts, ms.data(), num_motions * sizeof(int64_t), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(h->m_nframes, mn.data(), num_motions * sizeof(int64_t), hipMemcpyHostToDevice));
-    int64_t *d_cs = nullptr, *d_cn = nullptr;
-    float *d_cdt = nullptr, *scratch = nullptr;
-    HE_CHECK(dalloc(&d_cs, (size_t)num_clips));
-    HE_CHECK(dalloc(&d_cn, (size_t)num_clips));
-    HE_CHECK(dalloc(&d_cdt, (size_t)num_clips));
-    HE_CHECK(dalloc(&scratch, (size_t)F * B * 3));
-    HE_CHECK(hipMemcpy(d_cs, cstart.data(), num_clips * sizeof(int64_t), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(d_cn, cnf.data(), num_clips * sizeof(int64_t), hipMemcpyHostToDevice));
-    HE_CHECK(hipMemcpy(d_cdt, cdt.data(), num_clips * sizeof(float), hipMemcpyHostToDevice));
-    hipError_t e = launch_ingest(pose_quat_global, root_trans, h->d_model->parents, &h->d_model->local_pos[0][0],
-                                 d_cs, d_cn, d_cdt, num_clips, F, h->m_hot, h->m_cold, scratch, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(d_cs); hipFree(d_cn); hipFree(d_cdt); hipFree(scratch);
+    // the new tables and the kernel's temporaries in locals: every return frees what it leaves
+    // behind, and a failure leaves the loaded library in place
+    MotionTables t;
+    if (stage_motion_tables(t, F, num_motions, ml.data(), mdt.data(), ms.data(), mn.data())) return 1;
+    DeviceArray<int64_t> d_cs, d_cn;
+    DeviceArray<float> d_cdt, scratch;
+    HE_CHECK(d_cs.assign(cstart.data(), num_clips));
+    HE_CHECK(d_cn.assign(cnf.data(), num_clips));
+    HE_CHECK(d_cdt.assign(cdt.data(), num_clips));
+    HE_CHECK(scratch.alloc((size_t)F * HE_NUM_BODIES * 3));
+    const hipError_t e = launch_ingest(pose_quat_global, root_trans, h->d_model.get()->parents,
+                                       &h->d_model.get()->local_pos[0][0], d_cs, d_cn, d_cdt, num_clips, F, t.hot,
+                                       t.cold, scratch, st);
+    HE_CHECK(hipStreamSynchronize(st));  // before the temporaries go, whatever the launch said
     HE_CHECK(e);
-    HE_CHECK(e2);
-    h->m_frames = F;
-    h->m_motions = num_motions;
     HE_CHECK(invalidate_meta_cache(h));
+    h->motions = std::move(t);
     return 0;
 }
 
 namespace {
 static MotionDev motion_dev(he_engine* h) {
-    return MotionDev{h->m_hot, h->m_cold, h->m_starts, h->m_nframes, h->m_lengths, h->m_dt, h->m_motions};
+    const MotionTables& m = h->motions;
+    return MotionDev{m.hot, m.cold, m.starts, m.nframes, m.lengths, m.dt, m.count};
 }
 
 static int imit_common(he_engine* h, const he_imitation_params* p, const he_env_motion* em, ImitArgs& a, const char* what) {
     if (!h || !p || !em) return fail("%s: null argument", what);
     if (!h->num_envs) return fail("%s: no envs", what);
-    if (!h->m_motions) return fail("%s: call he_load_motions first", what);
+    if (!h->motions.count) return fail("%s: call he_load_motions first", what);
     if (!em->motion_ids || !em->start_times || !em->start_offsets || !em->global_offset || !em->progress)
         return fail("%s: he_env_motion has null buffers", what);
     a = ImitArgs{};
@@ -825,7 +784,7 @@ int he_amp_observations(int k, const float* root_pos, const float* root_rot, con
 int he_motion_state(he_engine* h, int k, const int64_t* ids, const float* times, const float* offset, float* rg_pos,
                     float* rb_rot, float* body_vel, float* body_ang_vel, float* dof_pos, float* dof_vel, void* stream) {
     if (!h) return fail("he_motion_state: null handle");
-    if (!h->m_motions) return fail("he_motion_state: call he_load_motions first");
+    if (!h->motions.count) return fail("he_motion_state: call he_load_motions first");
     if (k < 0 || (k > 0 && (!ids || !times))) return fail("he_motion_state: bad arguments");
     MotionStateArgs a{};
     a.m = motion_dev(h);

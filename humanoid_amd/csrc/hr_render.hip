@@ -10,13 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
+#include <memory>
+#include <utility>
 #include <vector>
 
 #include "../../include/humanoid_render.h"
+#include "he_host.h"
+#include "he_topo.h"
 
 namespace {
 
@@ -367,34 +368,17 @@ __global__ __launch_bounds__(256) void render_kernel(const Params P) {
     }
 }
 
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-#define HR_CHECK(expr)                                                                   \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(_e));       \
-    } while (0)
-
 }  // namespace
 
 struct hr_renderer {
     int device = 0;
     int num_envs = 0;
-    float* d_geom = nullptr;
-    float* d_mrgb = nullptr;  // [HR_MAX_MARKERS,3]
-    DCam* d_cams = nullptr;
+    DeviceArray<float> d_geom;
+    DeviceArray<float> d_mrgb;  // [HR_MAX_MARKERS,3]
+    DeviceArray<DCam> d_cams;
     int cam_cap = 0;
     int k = 0, W = 0, H = 0;
+    // borrowed from the caller (hr_set_appearance, hr_set_markers), who keeps them alive
     const float* body_rgb = nullptr;
     const int32_t* body_seg = nullptr;
     const float* mpos = nullptr;
@@ -404,47 +388,32 @@ struct hr_renderer {
 
 extern "C" {
 
-const char* hr_last_error(void) { return g_err.c_str(); }
+const char* hr_last_error(void) { return last_error(); }
 int hr_version(void) { return 1; }
 
 int hr_create(int device, const he_model* model, int num_envs, hr_renderer** out) {
     if (!out) return fail("hr_create: null output pointer");
     *out = nullptr;
-    if (!model) return fail("hr_create: null model");
+    if (check_model(model, "hr_create", HE_MAX_BOXES)) return 1;
     if (num_envs < 1) return fail("hr_create: num_envs %d < 1", num_envs);
-    if (model->num_bodies != NB) return fail("hr_create: the renderer draws %d bodies, the model has %d", NB, model->num_bodies);
     float geom[NB * kGeomWords];
     for (int b = 0; b < NB; ++b) {
-        const int32_t t = model->geom_type[b];
-        if (t != HE_GEOM_SPHERE && t != HE_GEOM_CAPSULE && t != HE_GEOM_BOX)
-            return fail("hr_create: body %d has geom type %d", b, t);
-        memcpy(&geom[b * kGeomWords], &t, sizeof(t));
+        memcpy(&geom[b * kGeomWords], &model->geom_type[b], sizeof(int32_t));
         memcpy(&geom[b * kGeomWords + 1], model->geom_params[b], 10 * sizeof(float));
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail("hr_create: no HIP device visible (the renderer has no CPU path)");
-    if (device < 0 || device >= count) return fail("hr_create: device %d of %d", device, count);
-    HR_CHECK(hipSetDevice(device));
-    hr_renderer* h = new hr_renderer;
+    if (select_device(device, "hr_create")) return 1;
+    std::unique_ptr<hr_renderer> h(new hr_renderer);  // a failed step below frees it and its arrays
     h->device = device;
     h->num_envs = num_envs;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_geom), sizeof(geom));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_mrgb), HR_MAX_MARKERS * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_geom, geom, sizeof(geom), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hr_destroy(h);
-        return fail("hr_create: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    HE_CHECK(h->d_geom.assign(geom, NB * kGeomWords));
+    HE_CHECK(h->d_mrgb.alloc(HR_MAX_MARKERS * 3));
+    *out = h.release();
     return 0;
 }
 
 int hr_destroy(hr_renderer* h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
-    if (h->d_geom) (void)hipFree(h->d_geom);
-    if (h->d_mrgb) (void)hipFree(h->d_mrgb);
-    if (h->d_cams) (void)hipFree(h->d_cams);
     delete h;
     return 0;
 }
@@ -482,15 +451,15 @@ int hr_set_cameras(hr_renderer* h, const hr_camera* c, int k) {
         dc[i].farp = c[i].far;
         for (int a = 0; a < 3; ++a) dc[i].pos[a] = c[i].pos[a], dc[i].target[a] = c[i].target[a];
     }
-    HR_CHECK(hipSetDevice(h->device));
+    HE_CHECK(hipSetDevice(h->device));
     if (k > h->cam_cap) {
-        DCam* p = nullptr;
-        HR_CHECK(hipMalloc(reinterpret_cast<void**>(&p), k * sizeof(DCam)));
-        if (h->d_cams) (void)hipFree(h->d_cams);
-        h->d_cams = p;
+        DeviceArray<DCam> p;
+        HE_CHECK(p.assign(dc.data(), k));
+        h->d_cams = std::move(p);
         h->cam_cap = k;
+    } else {
+        HE_CHECK(h->d_cams.upload(dc.data(), k));
     }
-    HR_CHECK(hipMemcpy(h->d_cams, dc.data(), k * sizeof(DCam), hipMemcpyHostToDevice));
     h->k = k;
     h->W = c[0].width;
     h->H = c[0].height;
@@ -514,8 +483,8 @@ int hr_set_markers(hr_renderer* h, const float* pos, int m, const float* host_rg
     }
     if (!pos || !host_rgb) return fail("hr_set_markers: null positions or colours");
     if (!(radius > 0.f)) return fail("hr_set_markers: radius %g is not positive", radius);
-    HR_CHECK(hipSetDevice(h->device));
-    HR_CHECK(hipMemcpy(h->d_mrgb, host_rgb, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HE_CHECK(hipSetDevice(h->device));
+    HE_CHECK(h->d_mrgb.upload(host_rgb, (size_t)m * 3));
     h->mpos = pos;
     h->m = m;
     h->mradius = radius;
@@ -548,7 +517,7 @@ int hr_render(hr_renderer* h, const float* rb_state, uint8_t* color, float* dept
     const dim3 grid((h->W + kTile - 1) / kTile, (h->H + kTile - 1) / kTile, h->k);
     if (grid.y > 65535u) return fail("hr_render: image height %d too large for one launch", h->H);
     hipLaunchKernelGGL(render_kernel, grid, dim3(kTile, kTile, 1), 0, static_cast<hipStream_t>(stream), P);
-    HR_CHECK(hipGetLastError());
+    HE_CHECK(hipGetLastError());
     return 0;
 }
 

@@ -28,7 +28,13 @@ FLAGS_DEFAULT = FLAG_ARMATURE
 JAC_ROWS = 6
 NG = 75  # HE_NUM_GEN: 6 root + 69 dof generalised velocities
 
-HD_SYMBOLS = ("hd_last_error", "hd_version", "hd_validate_model", "hd_create", "hd_destroy", "hd_compute")
+_V, _I = C.c_void_p, C.c_int
+# every exported symbol with its prototype (_abi.bind_library)
+HD_PROTOTYPES = {
+    "hd_last_error": (C.c_char_p, []), "hd_version": [], "hd_validate_model": [_V], "hd_create": [_I, _V, _V, _I, _V],
+    "hd_destroy": [_V], "hd_compute": [_V, _V, _V, _V, _V, _V, C.c_uint32, _V],
+}
+HD_SYMBOLS = tuple(HD_PROTOTYPES)
 
 
 class DynamicsError(RuntimeError):
@@ -38,23 +44,12 @@ class DynamicsError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """Load (never build) the dynamics library; it loads without a GPU."""
     global _lib
-    if _lib is not None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise DynamicsError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-    lib = C.CDLL(p)
-    V, I = C.c_void_p, C.c_int
-    lib.hd_last_error.restype = C.c_char_p
-    lib.hd_last_error.argtypes = []
-    sigs = {"hd_version": [], "hd_validate_model": [V], "hd_create": [I, V, V, I, V], "hd_destroy": [V],
-            "hd_compute": [V, V, V, V, V, V, C.c_uint32, V]}
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = I
-    _lib = lib
-    return lib
+    if _lib is None:
+        p = path or LIB_PATH
+        if not os.path.exists(p):
+            raise DynamicsError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+        _lib = _abi.bind_library(p, HD_PROTOTYPES)
+    return _lib
 
 
 def _check(rc):
@@ -69,16 +64,8 @@ def validate_model(he_model: _abi.HeModel):
 
 
 def check_tensor(t, dtype, shape, device, what):
-    """The check every tensor passes before its pointer is handed to the library: a contiguous tensor
-    of this dtype and shape on this device, else :class:`DynamicsError`. Returns the device pointer."""
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise DynamicsError(f"{what}: expected a torch tensor, got {type(t).__name__}")
-    if t.device != device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise DynamicsError(f"{what}: expected contiguous {dtype} {tuple(shape)} on {device}, got "
-                            f"{'contiguous' if t.is_contiguous() else 'non-contiguous'} {t.dtype} {tuple(t.shape)} "
-                            f"on {t.device}")
-    return C.c_void_p(t.data_ptr())
+    """_abi.check_tensor raising :class:`DynamicsError`."""
+    return _abi.check_tensor(t, dtype, shape, device, what, DynamicsError)
 
 
 def output_shapes(num_envs: int):
@@ -115,12 +102,7 @@ class Dynamics:
         self.bias = torch.zeros(shapes["bias"], dtype=torch.float32, device=self.device)
 
     def __del__(self):
-        try:
-            if getattr(self, "h", None) and self.lib is not None:
-                self.lib.hd_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        _abi.destroy_handle(self, "hd_destroy")
 
     @property
     def flags(self) -> int:

@@ -25,79 +25,53 @@ class EngineError(RuntimeError):
     pass
 
 
-HE_SYMBOLS = (
-    "he_last_error", "he_version", "he_device_count", "he_create", "he_set_model", "he_create_envs", "he_destroy",
-    "he_get_buffer", "he_set_dof_targets", "he_set_root_state_indexed", "he_set_dof_state_indexed",
-    "he_set_dof_targets_indexed", "he_set_env_properties", "he_simulate", "he_set_pd_params", "he_step_actions",
-    "he_refresh", "he_load_motions", "he_imitation_step", "he_motion_state", "he_reset_envs", "he_env_step",
-    "he_imitation_reset_step", "he_set_debug_stamps", "he_hash_uniform", "he_ingest_clips", "he_set_eval",
-    "he_set_amp", "he_amp_observations", "he_set_fused_step", "he_apply_body_forces", "he_apply_body_forces_at_pos",
-    "he_probe_masked_solves",
+_V, _I, _F, _I32, _I64, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_int32, C.c_int64, C.c_uint64
+# every exported symbol with its prototype (_abi.bind_library)
+HE_PROTOTYPES = {
+    "he_last_error": (C.c_char_p, []), "he_version": [], "he_device_count": [_V],
+    "he_hash_uniform": (_F, [_U64, _U64, C.c_uint32]),
+    "he_create": [_V, _I, _V], "he_set_model": [_V, _V], "he_create_envs": [_V, _I, _V], "he_destroy": [_V],
+    "he_get_buffer": [_V, _I, _V, _V, _V, _V], "he_set_dof_targets": [_V, _V, _V],
+    "he_set_root_state_indexed": [_V, _V, _V, _I, _V], "he_set_dof_state_indexed": [_V, _V, _V, _I, _V],
+    "he_set_dof_targets_indexed": [_V, _V, _V, _I, _V], "he_set_env_properties": [_V, _V, _V, _V],
+    "he_simulate": [_V, _I, _V], "he_set_pd_params": [_V, _V, _V, _V, _I], "he_step_actions": [_V, _V, _I, _V],
+    "he_refresh": [_V, _V],
+    "he_load_motions": [_V, _I64, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V],
+    "he_ingest_clips": [_V, _I, _V, _V, _V, _V, _I, _V, _V],
+    "he_imitation_step": [_V, _V, _V, _V, _V, _V, _V, _V, _V],
+    "he_motion_state": [_V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V],
+    "he_reset_envs": [_V, _V, _V, _V, _I, _V, _V, _V, _V, _V],
+    "he_env_step": [_V, _V, _V, _V, _I, _U64, _U64, _V, _V, _V, _V, _V, _V],
+    "he_imitation_reset_step": [_V, _V, _V, _U64, _U64, _V, _V, _V, _V, _V, _V],
+    "he_set_debug_stamps": [_V, _V], "he_set_eval": [_V, _V], "he_set_amp": [_V, _V], "he_set_fused_step": [_V, _I],
+    "he_amp_observations": [_I, _V, _V, _V, _V, _V, _V, _V, _V, _V],
+    **_abi.FORCE_PROTOTYPES, **_abi.PROBE_PROTOTYPES,
     # include/humanoid_rollout.h
-    "he_rollout_store", "he_rollout_order", "he_rollout_gather", "he_gae", "he_gae_minibatch", "he_episode_step",
-)
+    "he_rollout_store": [_V, _V, _I, _I64, _V, _V, _I64, _I32, _V],
+    "he_rollout_order": [_V, _I64, _V, _I, _V],
+    "he_rollout_gather": [_V, _I, _V, _I64, _I32, _I32, _I32, _V],
+    "he_gae": [_V, _V, _V, _I64, _F, _F, _V, _V],
+    "he_gae_minibatch": [_V, _V, _V, _V, _V, _I64, _F, _F, _I32, _I32, _I32, _V, _V, _V],
+    "he_episode_step": [_I32] + [_V] * 14,
+}
+HE_SYMBOLS = tuple(HE_PROTOTYPES)
 
 
 def load_library(path: Optional[str] = None):
     """Load (never build) the HIP engine library; raise loudly when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    # HE_ENGINE_LIB: diagnostics only (A/B timing of a variant build, tools/build_variant.py)
-    p = path or os.environ.get("HE_ENGINE_LIB") or LIB_PATH
-    if not os.path.exists(p):
-        raise EngineError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-    lib = C.CDLL(p)
-    V, I, F = C.c_void_p, C.c_int, C.c_float
-    lib.he_last_error.restype = C.c_char_p
-    lib.he_hash_uniform.restype = F
-    lib.he_hash_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
-    sigs = {
-        "he_create": [V, I, V], "he_set_model": [V, V], "he_create_envs": [V, I, V], "he_destroy": [V],
-        "he_get_buffer": [V, I, V, V, V, V], "he_set_dof_targets": [V, V, V],
-        "he_set_root_state_indexed": [V, V, V, I, V], "he_set_dof_state_indexed": [V, V, V, I, V],
-        "he_set_dof_targets_indexed": [V, V, V, I, V], "he_set_env_properties": [V, V, V, V],
-        "he_simulate": [V, I, V], "he_set_pd_params": [V, V, V, V, I], "he_step_actions": [V, V, I, V],
-        "he_refresh": [V, V],
-        "he_load_motions": [V, C.c_int64, I, V, V, V, V, V, V, V, V, V, V],
-        "he_ingest_clips": [V, I, V, V, V, V, I, V, V],
-        "he_imitation_step": [V, V, V, V, V, V, V, V, V],
-        "he_motion_state": [V, I, V, V, V, V, V, V, V, V, V, V],
-        "he_reset_envs": [V, V, V, V, I, V, V, V, V, V],
-        "he_env_step": [V, V, V, V, I, C.c_uint64, C.c_uint64, V, V, V, V, V, V],
-        "he_imitation_reset_step": [V, V, V, C.c_uint64, C.c_uint64, V, V, V, V, V, V],
-        "he_device_count": [V],
-        "he_set_debug_stamps": [V, V],
-        "he_set_eval": [V, V],
-        "he_set_amp": [V, V],
-        "he_set_fused_step": [V, I],
-        "he_amp_observations": [I, V, V, V, V, V, V, V, V, V],
-        "he_rollout_store": [V, V, I, C.c_int64, V, V, C.c_int64, C.c_int32, V],
-        "he_rollout_order": [V, C.c_int64, V, I, V],
-        "he_rollout_gather": [V, I, V, C.c_int64, C.c_int32, C.c_int32, C.c_int32, V],
-        "he_gae": [V, V, V, C.c_int64, F, F, V, V],
-        "he_gae_minibatch": [V, V, V, V, V, C.c_int64, F, F, C.c_int32, C.c_int32, C.c_int32, V, V, V],
-        "he_episode_step": [C.c_int32] + [V] * 14,
-    }
-    sigs.update(_abi.FORCE_PROTOTYPES)
-    sigs.update(_abi.PROBE_PROTOTYPES)
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = I
-    _lib = lib
-    return lib
+    if _lib is None:
+        # HE_ENGINE_LIB: diagnostics only (A/B timing of a variant build, tools/build_variant.py)
+        p = path or os.environ.get("HE_ENGINE_LIB") or LIB_PATH
+        if not os.path.exists(p):
+            raise EngineError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+        _lib = _abi.bind_library(p, HE_PROTOTYPES)
+    return _lib
 
 
 def _check(rc):
     if rc != 0:
         raise EngineError(_lib.he_last_error().decode())
-
-
-def _ptr(t) -> Optional[int]:
-    if t is None:
-        return None
-    return t.data_ptr()
 
 
 class _CudaArray:
@@ -147,12 +121,7 @@ class Engine:
         self.has_motions = False
 
     def __del__(self):
-        try:
-            if getattr(self, "h", None) and self.lib is not None:
-                self.lib.he_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        _abi.destroy_handle(self, "he_destroy")
 
     @property
     def stream(self):
@@ -232,30 +201,21 @@ class Engine:
         return self.buffer(_abi.BUF_PHYS_COST).clone()
 
     # ------------------------------------------------------------------ state writes
-    def _contig(self, t, dtype=None):
-        import torch
-        if t.device != self.device:
-            raise EngineError(f"tensor on {t.device}, engine on {self.device}")
-        if dtype is not None and t.dtype != dtype:
-            raise EngineError(f"expected {dtype}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise EngineError("Input tensor must be contiguous")  # wrapper.py:47-49
-        return t
+    def _dev(self, t, dtype, what, shape=None):
+        """The device pointer of a contiguous tensor of this dtype (and shape or element count) on the
+        engine's device (_abi.check_tensor; gymtorch refused non-contiguous tensors, wrapper.py:47-49)."""
+        return _abi.check_tensor(t, dtype, shape, self.device, what, EngineError)
 
     def set_dof_targets(self, t):
         import torch
-        t = self._contig(t, torch.float32)
-        if t.numel() != self.num_envs * _abi.ND:
-            raise EngineError("dof target tensor must hold num_envs*69 floats")
-        _check(self.lib.he_set_dof_targets(self.h, C.c_void_p(t.data_ptr()), self.stream))
+        _check(self.lib.he_set_dof_targets(self.h, self._dev(t, torch.float32, "dof targets", self.num_envs * _abi.ND),
+                                           self.stream))
 
     def _indexed(self, fn, src, ids, row):
         import torch
-        src = self._contig(src, torch.float32)
-        ids = self._contig(ids, torch.int32)
-        if src.numel() != self.num_envs * row:
-            raise EngineError("indexed writes take the full-size source tensor")
-        _check(fn(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(ids.data_ptr()), int(ids.numel()), self.stream))
+        p_src = self._dev(src, torch.float32, "indexed write's full-size source", self.num_envs * row)
+        p_ids = self._dev(ids, torch.int32, "indexed write's ids")
+        _check(fn(self.h, p_src, p_ids, int(ids.numel()), self.stream))
 
     def set_root_state_indexed(self, src, ids):
         self._indexed(self.lib.he_set_root_state_indexed, src, ids, 13)
@@ -269,9 +229,10 @@ class Engine:
     def set_env_properties(self, mass_scale=None, friction=None, terrain_kind=None):
         import torch
         self._env_props = (mass_scale, friction, terrain_kind)  # keep alive
-        vp = lambda t, dt: None if t is None else C.c_void_p(self._contig(t, dt).data_ptr())  # noqa: E731
-        _check(self.lib.he_set_env_properties(self.h, vp(mass_scale, torch.float32), vp(friction, torch.float32),
-                                              vp(terrain_kind, torch.int32)))
+        vp = lambda t, dt, what: None if t is None else self._dev(t, dt, what)  # noqa: E731
+        _check(self.lib.he_set_env_properties(self.h, vp(mass_scale, torch.float32, "mass_scale"),
+                                              vp(friction, torch.float32, "friction"),
+                                              vp(terrain_kind, torch.int32, "terrain_kind")))
 
     # ------------------------------------------------------------------ stepping
     def simulate(self, num_simulate: int = 2):
@@ -287,18 +248,18 @@ class Engine:
 
     def step_actions(self, actions, num_simulate: int = 2):
         import torch
-        a = self._contig(actions, torch.float32)
-        _check(self.lib.he_step_actions(self.h, C.c_void_p(a.data_ptr()), int(num_simulate), self.stream))
+        _check(self.lib.he_step_actions(self.h, self._dev(actions, torch.float32, "actions"), int(num_simulate),
+                                        self.stream))
 
     # ------------------------------------------------------------------ external wrenches
     def _body_rows(self, t, what):
         import torch
         if t is None:
             return None
-        t = self._contig(t, torch.float32)
+        p = self._dev(t, torch.float32, what)
         if tuple(t.shape) not in ((self.num_envs, _abi.NB, 3), (self.num_envs * _abi.NB, 3)):
             raise EngineError(f"{what} must be [num_envs,24,3] or [num_envs*24,3], got {tuple(t.shape)}")
-        return C.c_void_p(t.data_ptr())
+        return p
 
     def apply_body_forces(self, force=None, torque=None, space: int = _abi.SPACE_ENV, hold: int = 1):
         """gym.apply_rigid_body_force_tensors: forces (at the bodies' centres of mass) and torques,
@@ -358,10 +319,9 @@ class Engine:
     def motion_state(self, ids, times, offset=None, want_dof=True):
         import torch
         k = int(ids.numel())
-        ids = self._contig(ids, torch.int64)
-        times = self._contig(times, torch.float32)
-        if offset is not None:
-            offset = self._contig(offset, torch.float32)
+        p_ids = self._dev(ids, torch.int64, "motion ids")
+        p_times = self._dev(times, torch.float32, "motion times")
+        p_offset = None if offset is None else self._dev(offset, torch.float32, "offset")
         dev = self.device
         out = dict(rg_pos=torch.empty(k, 24, 3, device=dev), rb_rot=torch.empty(k, 24, 4, device=dev),
                    body_vel=torch.empty(k, 24, 3, device=dev), body_ang_vel=torch.empty(k, 24, 3, device=dev))
@@ -369,7 +329,7 @@ class Engine:
             out["dof_pos"] = torch.empty(k, 69, device=dev)
             out["dof_vel"] = torch.empty(k, 69, device=dev)
         vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-        _check(self.lib.he_motion_state(self.h, k, vp(ids), vp(times), vp(offset), vp(out["rg_pos"]), vp(out["rb_rot"]),
+        _check(self.lib.he_motion_state(self.h, k, p_ids, p_times, p_offset, vp(out["rg_pos"]), vp(out["rb_rot"]),
                                         vp(out["body_vel"]), vp(out["body_ang_vel"]), vp(out.get("dof_pos")),
                                         vp(out.get("dof_vel")), self.stream))
         return out
@@ -378,15 +338,11 @@ class Engine:
         """Per-env motion bookkeeping block; the returned struct keeps the tensors alive."""
         import torch
         n = self.num_envs
-        checks = ((motion_ids, torch.int64, (n,)), (start_times, torch.float32, (n,)),
-                  (start_offsets, torch.float32, (n,)), (global_offset, torch.float32, (n, 3)),
-                  (progress, torch.int16, (n,)))
-        for t, dt, shape in checks:
-            self._contig(t, dt)
-            if tuple(t.shape) != shape:
-                raise EngineError(f"env motion buffer has shape {tuple(t.shape)}, expected {shape}")
-        em = _abi.HeEnvMotion(motion_ids.data_ptr(), start_times.data_ptr(), start_offsets.data_ptr(),
-                              global_offset.data_ptr(), progress.data_ptr())
+        checks = (("motion_ids", motion_ids, torch.int64, (n,)), ("start_times", start_times, torch.float32, (n,)),
+                  ("start_offsets", start_offsets, torch.float32, (n,)),
+                  ("global_offset", global_offset, torch.float32, (n, 3)), ("progress", progress, torch.int16, (n,)))
+        em = _abi.HeEnvMotion(*[self._dev(t, dt, f"env motion buffer {what}", shape).value
+                                for what, t, dt, shape in checks])
         em.keep_alive = (motion_ids, start_times, start_offsets, global_offset, progress)
         return em
 
@@ -398,17 +354,17 @@ class Engine:
 
     def reset_envs(self, params, em, env_ids, phases, obs, reset, terminate):
         import torch
-        env_ids = self._contig(env_ids, torch.int32)
-        phases = self._contig(phases, torch.float32)
-        _check(self.lib.he_reset_envs(self.h, C.byref(params), C.byref(em), C.c_void_p(env_ids.data_ptr()),
-                                      int(env_ids.numel()), C.c_void_p(phases.data_ptr()), C.c_void_p(obs.data_ptr()),
+        p_ids = self._dev(env_ids, torch.int32, "env_ids")
+        p_phases = self._dev(phases, torch.float32, "phases")
+        _check(self.lib.he_reset_envs(self.h, C.byref(params), C.byref(em), p_ids,
+                                      int(env_ids.numel()), p_phases, C.c_void_p(obs.data_ptr()),
                                       C.c_void_p(reset.data_ptr()), C.c_void_p(terminate.data_ptr()), self.stream))
 
     def env_step(self, params, em, actions, obs, rew, reward_raw, reset, terminate, seed: int, step_index: int,
                  num_simulate: int = 2):
         import torch
-        a = self._contig(actions, torch.float32)
-        _check(self.lib.he_env_step(self.h, C.byref(params), C.byref(em), C.c_void_p(a.data_ptr()), int(num_simulate),
+        a = self._dev(actions, torch.float32, "actions")
+        _check(self.lib.he_env_step(self.h, C.byref(params), C.byref(em), a, int(num_simulate),
                                     C.c_uint64(seed), C.c_uint64(step_index), C.c_void_p(obs.data_ptr()),
                                     C.c_void_p(rew.data_ptr()), C.c_void_p(reward_raw.data_ptr()),
                                     C.c_void_p(reset.data_ptr()), C.c_void_p(terminate.data_ptr()), self.stream))
@@ -442,7 +398,7 @@ class Engine:
         for t in (amp_obs, amp_obs_demo):
             if t is None:
                 continue
-            self._contig(t, torch.float32)
+            self._dev(t, torch.float32, "AMP buffer")
             if t.dim() != 3 or t.shape[0] != self.num_envs or t.shape[2] != _abi.AMP_OBS_STEP:
                 raise EngineError(f"AMP buffer has shape {tuple(t.shape)}, expected [{self.num_envs}, S, 196]")
         if amp_obs_demo is not None and amp_obs_demo.shape != amp_obs.shape:
@@ -456,7 +412,7 @@ class Engine:
         """Diagnostics: int64 [num_envs, 32] (HE_STAMP_SLOTS) device tensor receiving per-phase cycles, or None."""
         import torch
         if buf is not None:
-            self._contig(buf, torch.int64)
+            self._dev(buf, torch.int64, "debug stamps")
         self._stamps = buf
         _check(self.lib.he_set_debug_stamps(self.h, None if buf is None else C.c_void_p(buf.data_ptr())))
 
@@ -473,11 +429,9 @@ def amp_observations(root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_ve
     ins = (root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, key_body_pos)
     shapes = ((k, 3), (k, 4), (k, 3), (k, 3), (k, 69), (k, 69), (k, 4, 3))
     dev = root_pos.device
-    for t, sh in zip(ins, shapes):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != sh:
-            raise EngineError(f"he_amp_observations: expected contiguous f32 {sh} on {dev}, got "
-                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    ptrs = [_abi.check_tensor(t, torch.float32, sh, dev, "he_amp_observations", EngineError)
+            for t, sh in zip(ins, shapes)]
     out = torch.empty(k, _abi.AMP_OBS_STEP, device=dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _check(lib.he_amp_observations(k, *[C.c_void_p(t.data_ptr()) for t in ins], C.c_void_p(out.data_ptr()), stream))
+    _check(lib.he_amp_observations(k, *ptrs, C.c_void_p(out.data_ptr()), stream))
     return out

@@ -29,8 +29,14 @@ MAX_MARKERS = 24
 FOLLOW_POSITION, FOLLOW_TRANSFORM, FOLLOW_POSITION_XY = 0, 1, 2
 BODY_RGB = (0.80, 0.68, 0.52)
 
-HR_SYMBOLS = ("hr_last_error", "hr_version", "hr_create", "hr_destroy", "hr_validate_cameras", "hr_set_cameras",
-              "hr_set_appearance", "hr_set_markers", "hr_render")
+_V, _I = C.c_void_p, C.c_int
+# every exported symbol with its prototype (_abi.bind_library)
+HR_PROTOTYPES = {
+    "hr_last_error": (C.c_char_p, []), "hr_version": [], "hr_create": [_I, _V, _I, _V], "hr_destroy": [_V],
+    "hr_validate_cameras": [_V, _I, _I], "hr_set_cameras": [_V, _V, _I], "hr_set_appearance": [_V, _V, _V],
+    "hr_set_markers": [_V, _V, _I, _V, C.c_float], "hr_render": [_V, _V, _V, _V, _V, C.c_uint32, _V],
+}
+HR_SYMBOLS = tuple(HR_PROTOTYPES)
 
 
 class RenderError(RuntimeError):
@@ -59,24 +65,12 @@ def camera(env: int, width: int, height: int, pos, target, hfov_deg: float = 90.
 def load_library(path: Optional[str] = None):
     """Load (never build) the render library; it loads without a GPU."""
     global _lib
-    if _lib is not None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise RenderError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-    lib = C.CDLL(p)
-    V, I, F = C.c_void_p, C.c_int, C.c_float
-    lib.hr_last_error.restype = C.c_char_p
-    lib.hr_last_error.argtypes = []
-    sigs = {"hr_version": [], "hr_create": [I, V, I, V], "hr_destroy": [V], "hr_validate_cameras": [V, I, I],
-            "hr_set_cameras": [V, V, I], "hr_set_appearance": [V, V, V], "hr_set_markers": [V, V, I, V, F],
-            "hr_render": [V, V, V, V, V, C.c_uint32, V]}
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = I
-    _lib = lib
-    return lib
+    if _lib is None:
+        p = path or LIB_PATH
+        if not os.path.exists(p):
+            raise RenderError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+        _lib = _abi.bind_library(p, HR_PROTOTYPES)
+    return _lib
 
 
 def _check(rc):
@@ -116,18 +110,10 @@ class Renderer:
         self._markers = None
 
     def __del__(self):
-        try:
-            if getattr(self, "h", None) and self.lib is not None:
-                self.lib.hr_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        _abi.destroy_handle(self, "hr_destroy")
 
-    def _dev(self, t, dtype, shape, what):
-        if t.device != self.device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise RenderError(f"{what}: expected contiguous {dtype} {tuple(shape)} on {self.device}, got {t.dtype} "
-                              f"{tuple(t.shape)} on {t.device}")
-        return C.c_void_p(t.data_ptr())
+    def _dev(self, t, dtype, shape, what, at_least=None):
+        return _abi.check_tensor(t, dtype, shape, self.device, what, RenderError, at_least)
 
     def set_cameras(self, cams: Sequence[HrCamera]):
         """Replace the camera set (all of one size). A refused set raises and leaves the previous one."""
@@ -170,11 +156,18 @@ class Renderer:
 
     def render_into(self, color=None, depth=None, seg=None, flags: int = FLAGS_DEFAULT, rb_state=None):
         """hr_render into caller tensors (``None``: that output is not written). ``rb_state`` defaults to
-        the engine's live buffer."""
-        rb = self.engine.rb_state if rb_state is None else rb_state
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _check(self.lib.hr_render(self.h, C.c_void_p(rb.data_ptr()), vp(color), vp(depth), vp(seg), int(flags),
-                                  self.engine.stream))
+        the engine's live buffer. The kernel writes K*H*W pixels into each output and reads every env's 24
+        rigid-body rows: every tensor is checked to be on the device, contiguous, of its dtype (``color``
+        uint8 x 4 per pixel, ``depth`` float32, ``seg`` int32) and at least that long before any pointer
+        is passed; longer, or of another shape, is the caller's business."""
+        import torch
+        n = self.num_cameras * self.height * self.width
+        p_color = None if color is None else self._dev(color, torch.uint8, None, "color", 4 * n)
+        p_depth = None if depth is None else self._dev(depth, torch.float32, None, "depth", n)
+        p_seg = None if seg is None else self._dev(seg, torch.int32, None, "seg", n)
+        p_rb = self._dev(self.engine.rb_state if rb_state is None else rb_state, torch.float32, None, "rb_state",
+                         self.num_envs * _abi.NB * 13)
+        _check(self.lib.hr_render(self.h, p_rb, p_color, p_depth, p_seg, int(flags), self.engine.stream))
 
     def render(self, flags: int = FLAGS_DEFAULT):
         """Draw every camera into ``color`` / ``depth`` / ``seg`` (one launch, no host synchronisation)."""

@@ -85,6 +85,66 @@ def test_create_without_gpu_reports(he_model):
     assert lib.hr_create(0, C.byref(he_model), 0, C.byref(h)) != 0 and "num_envs" in lib.hr_last_error().decode()
 
 
+def test_create_refuses_a_model_the_engine_would_refuse(he_model):
+    """hr_create runs the structural model check the engine and the dynamics library run, and says why."""
+    import copy
+    lib = _lib()
+    h = C.c_void_p()
+    for index, parent, word in ((0, 0, "root"), (5, 7, "DFS")):
+        m = copy.deepcopy(he_model)
+        m.parents[index] = parent
+        assert lib.hr_create(0, C.byref(m), 4, C.byref(h)) != 0 and not h.value
+        text = lib.hr_last_error().decode()
+        assert text.startswith("hr_create: ") and word in text, text
+    for field, value, word in (("num_bodies", 23, "bodies"), ("num_dof", 68, "dofs"), ("num_pairs", 257, "pair")):
+        m = copy.deepcopy(he_model)
+        setattr(m, field, value)
+        assert lib.hr_create(0, C.byref(m), 4, C.byref(h)) != 0 and word in lib.hr_last_error().decode()
+    m = copy.deepcopy(he_model)
+    m.geom_type[3] = 9
+    assert lib.hr_create(0, C.byref(m), 4, C.byref(h)) != 0 and "geom type 9" in lib.hr_last_error().decode()
+
+
+class _NoCalls:
+    """Stands in for the library: any call is a failure of the check under test."""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"library call {name} before the argument check")
+
+
+def test_render_into_checks_tensors_before_any_library_call():
+    """render_into hands the kernel raw pointers it writes K*H*W pixels through: a tensor that is not on the
+    device, of another dtype, non-contiguous, no tensor at all or too short is refused by name first."""
+    import torch
+    from humanoid_amd import render
+    k, hgt, w, n_envs = 2, 5, 7, 3
+    n = k * hgt * w
+    r = object.__new__(render.Renderer)
+    r.lib, r.h, r.engine = _NoCalls(), None, None
+    r.num_cameras, r.height, r.width, r.num_envs = k, hgt, w, n_envs
+    good = {"color": torch.zeros(4 * n, dtype=torch.uint8), "depth": torch.zeros(n), "seg": torch.zeros(n, dtype=torch.int32),
+            "rb_state": torch.zeros(n_envs * 24, 13)}
+    wrong_dtype = {"color": torch.float32, "depth": torch.float64, "seg": torch.int64, "rb_state": torch.float64}
+    for name, ok in good.items():
+        bad = {
+            "a CPU tensor": (torch.device("cuda", 0), ok),
+            "a wrong dtype": (torch.device("cpu"), ok.to(wrong_dtype[name])),
+            "non-contiguous": (torch.device("cpu"), torch.stack([ok, ok], -1)[..., 0]),
+            "not a tensor": (torch.device("cpu"), ok.numpy()),
+            "too short": (torch.device("cpu"), ok.reshape(-1)[:-1]),
+        }
+        for what, (device, t) in bad.items():
+            r.device = device
+            assert what != "non-contiguous" or not t.is_contiguous()
+            with pytest.raises(render.RenderError, match=name):
+                r.render_into(**{name: t})
+    # tensors that pass reach the library call, and only then: flat and longer than needed is accepted
+    r.device = torch.device("cpu")
+    long = {name: torch.cat([t.reshape(-1), t.reshape(-1)]) for name, t in good.items()}
+    with pytest.raises(AssertionError, match="library call hr_render"):
+        r.render_into(**long)
+
+
 def test_invalid_camera_sets_are_refused():
     from humanoid_amd import render
     lib = _lib()
