@@ -49,6 +49,14 @@ FORCE_PROTOTYPES = {
     "he_apply_body_forces": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "he_apply_body_forces_at_pos": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
 }
+# include/humanoid_engine.h HE_DOF_MODE_* (gymapi.DOF_MODE_*): the drive mode of a dof (he_set_dof_drive_modes)
+DOF_MODE_NONE, DOF_MODE_POS, DOF_MODE_VEL, DOF_MODE_EFFORT = 0, 1, 2, 3
+# torque control: (engine, host modes [69]); (engine, src [N,69] or NULL, stream); (engine, src, ids, k, stream)
+ACTUATION_PROTOTYPES = {
+    "he_set_dof_drive_modes": [C.c_void_p, C.c_void_p],
+    "he_set_dof_actuation_forces": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "he_set_dof_actuation_forces_indexed": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+}
 # the solve probe: factor, y, n, out, stream
 PROBE_PROTOTYPES = {
     "he_probe_masked_solves": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],

@@ -93,6 +93,13 @@ struct he_engine {
     // by the next call, not accumulated into)
     DeviceArray<float> wrench;
     int wrench_hold = 0;
+    // torque control (he_set_dof_drive_modes, he_set_dof_actuation_forces): the dofs' drive modes (`model`
+    // keeps the caller's gains; d_model has zero gains on the dofs that are not POS), and the engine's
+    // own [N,69] clamped actuation, handed to the physics launches while act_set
+    int32_t modes[HE_NUM_DOF] = {};
+    DeviceArray<int32_t> d_modes;
+    DeviceArray<float> dof_act;
+    bool act_set = false;
 
     ~he_engine() {
         if (order_ready) (void)hipEventDestroy(order_ready);
@@ -127,6 +134,7 @@ std::vector<EnvBuffer> env_buffers(he_engine* h) {
         {HE_BUF_PHYS_COST, &h->cost, 1, 0, I32, 0},
         {-1, &h->meta_cache, 1, 8, I32, 0xFF},  // motion -1: empty
         {-1, &h->wrench, NB, 6, F32, 0},
+        {-1, &h->dof_act, 1, ND, F32, 0},
     };
 }
 }  // namespace
@@ -186,6 +194,13 @@ int he_set_model(he_engine* h, const he_model* model) {
     HE_CHECK(d_model.assign(model, 1));
     HE_CHECK(d_topo.assign(&topo, 1));
     HE_CHECK(d_rest.assign(&rest[0][0], HE_NUM_BODIES * 3));
+    int32_t modes[HE_NUM_DOF];
+    for (int d = 0; d < HE_NUM_DOF; ++d) modes[d] = HE_DOF_MODE_POS;
+    DeviceArray<int32_t> d_modes;
+    HE_CHECK(d_modes.assign(modes, HE_NUM_DOF));
+    h->d_modes = std::move(d_modes);
+    std::memcpy(h->modes, modes, sizeof(modes));
+    h->act_set = false;
     h->d_model = std::move(d_model);
     h->d_topo = std::move(d_topo);
     h->d_rest = std::move(d_rest);
@@ -403,6 +418,7 @@ static PhysArgs phys_args(he_engine* h, int num_simulate, const float* actions) 
         a.ext_steps = cover * h->params.substeps;
         h->wrench_hold -= cover;
     }
+    a.dof_act = h->act_set ? h->dof_act.get() : nullptr;
     return a;
 }
 
@@ -439,6 +455,73 @@ int he_apply_body_forces(he_engine* h, const float* force, const float* torque, 
 }
 int he_apply_body_forces_at_pos(he_engine* h, const float* force, const float* pos, int space, int hold, void* stream) {
     return apply_wrench(h, force, pos, 1, space, hold, stream, "he_apply_body_forces_at_pos");
+}
+
+// Drive modes: the device model again with zero gains on the dofs that are not POS (drive_terms then
+// yields tau = 0, coef = 0 and an effort scale of 1 there: no kernel knows about modes), the modes for
+// the actuation's preparation kernel. Built in locals and moved in after the last step.
+int he_set_dof_drive_modes(he_engine* h, const int32_t* host_modes) {
+    if (!h) return fail("he_set_dof_drive_modes: null handle");
+    if (!host_modes) return fail("he_set_dof_drive_modes: null modes");
+    if (!h->has_model) return fail("he_set_dof_drive_modes: call he_set_model first");
+    for (int d = 0; d < HE_NUM_DOF; ++d) {
+        const int m = host_modes[d];
+        if (m == HE_DOF_MODE_VEL)
+            return fail("he_set_dof_drive_modes: dof %d asks for DOF_MODE_VEL (2): the engine has no velocity "
+                        "target tensor; use 0 (NONE), 1 (POS) or 3 (EFFORT)", d);
+        if (m != HE_DOF_MODE_NONE && m != HE_DOF_MODE_POS && m != HE_DOF_MODE_EFFORT)
+            return fail("he_set_dof_drive_modes: dof %d has mode %d, out of range: 0 (NONE), 1 (POS) or 3 (EFFORT)", d, m);
+    }
+    he_model dev = h->model;
+    for (int d = 0; d < HE_NUM_DOF; ++d)
+        if (host_modes[d] != HE_DOF_MODE_POS) dev.stiffness[d] = dev.damping[d] = 0.f;
+    HE_CHECK(hipSetDevice(h->device));
+    DeviceArray<he_model> d_model;
+    DeviceArray<int32_t> d_modes;
+    HE_CHECK(d_model.assign(&dev, 1));
+    HE_CHECK(d_modes.assign(host_modes, HE_NUM_DOF));
+    h->d_model = std::move(d_model);  // releasing the old copies waits for the launches that read them
+    h->d_modes = std::move(d_modes);
+    std::memcpy(h->modes, host_modes, sizeof(h->modes));
+    h->act_set = false;
+    return 0;
+}
+
+namespace {
+static int set_actuation(he_engine* h, const float* src, const int32_t* ids, int k, bool indexed, void* stream,
+                         const char* what) {
+    if (!h) return fail("%s: null handle", what);
+    if (!h->num_envs) return fail("%s: no envs created", what);
+    if (indexed) {
+        if (!src || !ids) return fail("%s: null argument", what);
+        if (k < 0) return fail("%s: negative count", what);
+        if (k == 0) return 0;
+    } else if (!src) {  // clear
+        h->act_set = false;
+        return 0;
+    }
+    const size_t n = (size_t)h->num_envs * HE_NUM_DOF;
+    // rows an indexed write does not list keep what was set, or zero when nothing was
+    if (indexed && !h->act_set) HE_CHECK(hipMemsetAsync(h->dof_act, 0, n * sizeof(float), (hipStream_t)stream));
+    DofActArgs a{};
+    a.src = src;
+    a.ids = indexed ? ids : nullptr;
+    a.modes = h->d_modes;
+    a.model = h->d_model;
+    a.act = h->dof_act;
+    a.count = indexed ? k : h->num_envs;
+    a.num_envs = h->num_envs;
+    HE_CHECK(launch_dof_actuation(a, (hipStream_t)stream));
+    h->act_set = true;
+    return 0;
+}
+}  // namespace
+
+int he_set_dof_actuation_forces(he_engine* h, const float* src, void* stream) {
+    return set_actuation(h, src, nullptr, 0, false, stream, "he_set_dof_actuation_forces");
+}
+int he_set_dof_actuation_forces_indexed(he_engine* h, const float* src, const int32_t* ids, int k, void* stream) {
+    return set_actuation(h, src, ids, k, true, stream, "he_set_dof_actuation_forces_indexed");
 }
 
 // the physics launch, then every order_every launches the next launches' dispatch order from this

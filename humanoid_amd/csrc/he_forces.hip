@@ -1,5 +1,6 @@
 // he_forces.hip -- external wrench preparation for gfx950 (he_apply_body_forces and
-// he_apply_body_forces_at_pos; gym.apply_rigid_body_force_tensors, puffer_phc/envs/render_env.py:105-126).
+// he_apply_body_forces_at_pos; gym.apply_rigid_body_force_tensors, puffer_phc/envs/render_env.py:105-126)
+// and the dof actuation forces' (he_set_dof_actuation_forces; dof_actuation_kernel below).
 //
 // One thread per body row: the caller's (force, torque) or (force, application point) rows in
 // `space` and the body's current rigid-body row become the engine's world-axis (torque, force at the
@@ -14,6 +15,7 @@
 namespace {
 
 constexpr int NB = HE_NUM_BODIES;
+constexpr int ND = HE_NUM_DOF;
 
 __global__ void __launch_bounds__(256) body_wrench_kernel(WrenchArgs a) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,6 +53,19 @@ __global__ void __launch_bounds__(256) body_wrench_kernel(WrenchArgs a) {
     w[3] = f.x; w[4] = f.y; w[5] = f.z;
 }
 
+// One thread per (row, dof): the actuation the physics kernels add to Q[6 + d]
+__global__ void __launch_bounds__(256) dof_actuation_kernel(DofActArgs a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.count * ND) return;
+    const int i = t / ND, d = t - i * ND;
+    const int e = a.ids ? a.ids[i] : i;
+    if (e < 0 || e >= a.num_envs) return;
+    const size_t o = (size_t)e * ND + d;
+    const float lim = a.model->effort[d];
+    const float v = a.src[o];
+    a.act[o] = a.modes[d] == HE_DOF_MODE_EFFORT ? fminf(fmaxf(v, -lim), lim) : 0.f;
+}
+
 __global__ void warm_tu_kernel() {}
 }  // namespace
 
@@ -61,11 +76,20 @@ hipError_t warm_forces_kernels(hipStream_t stream, int mode) {
     }
     WrenchArgs wa{};
     body_wrench_kernel<<<1, 256, 0, stream>>>(wa);  // rows 0: every thread leaves at the guard
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    DofActArgs da{};
+    dof_actuation_kernel<<<1, 256, 0, stream>>>(da);  // count 0 likewise
     return hipGetLastError();
 }
 
 hipError_t launch_body_wrench(const WrenchArgs& a, hipStream_t stream) {
     if (a.rows <= 0) return hipSuccess;
     body_wrench_kernel<<<(a.rows + 255) / 256, 256, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_dof_actuation(const DofActArgs& a, hipStream_t stream) {
+    if (a.count <= 0) return hipSuccess;
+    dof_actuation_kernel<<<(a.count * ND + 255) / 256, 256, 0, stream>>>(a);
     return hipGetLastError();
 }

@@ -120,6 +120,10 @@ struct PhysArgs {
     // pending, and launch_physics runs the kernels without the wrench code
     const float* ext_wrench;
     int ext_steps;
+    // dof actuation forces (he_set_dof_actuation_forces): the engine's [N,69] clamped joint torques, added
+    // to the generalized force of every physics step of the launch; null: none set. Non-null selects the
+    // kernels with the wrench code too (launch_physics)
+    const float* dof_act;
 };
 
 // he_apply_body_forces / he_apply_body_forces_at_pos: (force, torque | application point, space) and
@@ -138,6 +142,21 @@ struct WrenchArgs {
     int accumulate;
 };
 hipError_t launch_body_wrench(const WrenchArgs& a, hipStream_t stream);
+
+// he_set_dof_actuation_forces(_indexed): the caller's [N,69] joint torques into the engine's own
+// array, row by row: on EFFORT dofs (modes[d] == HE_DOF_MODE_EFFORT) the source clamped to
+// +-model.effort[d], on every other dof 0. ids null: rows 0..count-1; else rows ids[0..count), an id
+// outside [0, num_envs) skipped.
+struct DofActArgs {
+    const float* src;        // [N,69]
+    const int32_t* ids;      // [count] or null
+    const int32_t* modes;    // [69] HE_DOF_MODE_*
+    const he_model* model;   // device copy (the effort limits)
+    float* act;              // [N,69]
+    int count;
+    int num_envs;
+};
+hipError_t launch_dof_actuation(const DofActArgs& a, hipStream_t stream);
 
 hipError_t launch_imitation(const ImitArgs& a, hipStream_t stream);
 hipError_t launch_amp(const AmpArgs& a, hipStream_t stream);

@@ -90,7 +90,7 @@ struct Lds {
     int8_t srow0[MAXC];            // first solver row of each slot
     int8_t rslot[W], rkind[W];     // solver row -> its slot, its kind (0 normal / limit, 1 2 tangential, 3 torsional)
     BodyTopo T;
-    float Q[NG];  // external wrenches' generalized force of this physics step (ext_wrench_terms; the EXT kernels only)
+    float Q[NG];  // external wrenches' and dof actuations' generalized force of this physics step (ext_wrench_terms; the EXT kernels only)
 };
 
 // wave priority: s_setprio 3 over the serial chains (PGS rows, the elimination, the L^-T sweeps;
@@ -1507,11 +1507,24 @@ HE_DEV void body_forces(Lds& L, const he_model& m, const he_sim_params& p, int l
 // subtree sums by body levels; Q_i = S_i . sum_subtree(body(i)) W into L.Q. Acc is scratch (dead from
 // body_forces to the midpoint bias / the contact phase). on == false (the launch's physics steps past
 // the wrench's hold): Q = 0, and the step computes what the kernels without the wrench code compute.
+// The dof actuation forces (he_set_dof_actuation_forces; PhysArgs.dof_act non-null) then add the env's
+// clamped joint torques to Q[6..75), in every physics step of the launch: the row is loaded from
+// global memory here (lane i adds dof i - 6 to Q[i], then lanes 0..10 dofs 58..68 to Q[64..74]), nothing
+// is kept between phases.
+HE_DEV void ext_actuation_terms(Lds& L, const PhysArgs& a, int lane) {
+    if (a.dof_act) {  // wave-uniform (a launch argument)
+        const float* row = a.dof_act + (size_t)L.sch_e * ND;  // the env from LDS: no register held
+        if (lane >= 6) L.Q[lane] += row[lane >= 6 ? lane - 6 : 0];
+        if (lane < NG - W) L.Q[W + lane] += row[W - 6 + lane];
+        sync();
+    }
+}
 HE_DEV void ext_wrench_terms(Lds& L, const he_model& m, const PhysArgs& a, int lane, bool on) {
-    if (!on) {  // wave-uniform
+    if (!on || !a.ext_wrench) {  // wave-uniform; an actuation alone runs without a wrench array
         L.Q[lane] = 0.f;
         if (lane < NG - W) L.Q[W + lane] = 0.f;
         sync();
+        ext_actuation_terms(L, a, lane);
         return;
     }
     if (lane < NB) {
@@ -1529,6 +1542,17 @@ HE_DEV void ext_wrench_terms(Lds& L, const he_model& m, const PhysArgs& a, int l
     L.Q[lane] = dot6(L.S[lane], L.Acc[dof_body(lane)]);
     if (lane < NG - W) L.Q[W + lane] = dot6(L.S[W + lane], L.Acc[(W + lane - 6) / 3 + 1]);
     sync();
+    ext_actuation_terms(L, a, lane);
+}
+// HE_BUF_DOF_FORCE includes the applied actuation (the EXT kernels, after the solver's drive and limit
+// forces are final): dforce[d] += the env's row, re-read from global memory. Ends on a sync.
+HE_DEV void ext_actuation_out(Lds& L, const PhysArgs& a, int lane) {
+    if (a.dof_act) {  // wave-uniform
+        const float* row = a.dof_act + (size_t)L.sch_e * ND;
+        L.dforce[lane] += row[lane];
+        if (lane < ND - W) L.dforce[W + lane] += row[W + lane];
+        sync();
+    }
 }
 
 // Bias forces, IS_i = Ic S_i and the implicit PD drives (oracle: the drive block), lane = dof, then
@@ -2700,11 +2724,17 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     if (!TGS && nr == 0) free_velocity(L, T, lane);
     STAMP(PH_DU_SOLVE);
     if constexpr (TGS) {  // TGS: the iterations integrated the positions and set the drive force
+        if constexpr (EXT) {
+            if (last) ext_actuation_out(L, a, lane);
+        }
         STAMP(PH_INTEGRATE);
         return;
     }
     // ---- PGS: drive force actually applied, damping, clamps, write velocities
     if (last) pgs_drive_out(L, lane, nr, dt);
+    if constexpr (EXT) {
+        if (last) ext_actuation_out(L, a, lane);
+    }
     integrate_bodies(L, T, lane, p, dt, damp, L.uf, true, !last);
     STAMP(PH_INTEGRATE);
 }
@@ -2924,8 +2954,9 @@ HE_DEV void physics_body(const PhysArgs& a) {
 // register plan does not touch the PGS kernel's
 __global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel(PhysArgs a) { physics_body<false, false>(a); }
 __global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs(PhysArgs a) { physics_body<true, false>(a); }
-// the same steps with external wrenches (PhysArgs.ext_wrench, he_apply_body_forces): launched only while
-// a wrench is pending, so every other launch runs the two kernels above unchanged
+// the same steps with external wrenches (PhysArgs.ext_wrench, he_apply_body_forces) and dof actuation
+// forces (PhysArgs.dof_act, he_set_dof_actuation_forces): launched only while a wrench is pending or an
+// actuation is set, so every other launch runs the two kernels above unchanged
 __global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_ext(PhysArgs a) { physics_body<false, true>(a); }
 __global__ void __launch_bounds__(64, HE_MIN_WAVES) physics_kernel_tgs_ext(PhysArgs a) { physics_body<true, true>(a); }
 
@@ -3078,7 +3109,7 @@ hipError_t launch_physics_order(const uint32_t* cost, int32_t* order, int num_en
 hipError_t launch_physics(const PhysArgs& a, hipStream_t stream) {
     if (a.num_envs <= 0) return hipSuccess;
     const size_t lds = physics_lds_bytes();
-    const bool ext = a.ext_wrench && a.ext_steps > 0;  // a wrench pending for this launch
+    const bool ext = (a.ext_wrench && a.ext_steps > 0) || a.dof_act;  // a wrench pending or an actuation set
     if (ext && a.p.solver_type == 1) physics_kernel_tgs_ext<<<a.num_envs, W, lds, stream>>>(a);
     else if (ext) physics_kernel_ext<<<a.num_envs, W, lds, stream>>>(a);
     else if (a.p.solver_type == 1) physics_kernel_tgs<<<a.num_envs, W, lds, stream>>>(a);

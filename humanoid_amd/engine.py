@@ -45,7 +45,7 @@ HE_PROTOTYPES = {
     "he_imitation_reset_step": [_V, _V, _V, _U64, _U64, _V, _V, _V, _V, _V, _V],
     "he_set_debug_stamps": [_V, _V], "he_set_eval": [_V, _V], "he_set_amp": [_V, _V], "he_set_fused_step": [_V, _I],
     "he_amp_observations": [_I, _V, _V, _V, _V, _V, _V, _V, _V, _V],
-    **_abi.FORCE_PROTOTYPES, **_abi.PROBE_PROTOTYPES,
+    **_abi.FORCE_PROTOTYPES, **_abi.ACTUATION_PROTOTYPES, **_abi.PROBE_PROTOTYPES,
     # include/humanoid_rollout.h
     "he_rollout_store": [_V, _V, _I, _I64, _V, _V, _I64, _I32, _V],
     "he_rollout_order": [_V, _I64, _V, _I, _V],
@@ -277,6 +277,40 @@ class Engine:
     def clear_body_forces(self):
         """Drop the pending wrench: the next launch runs without one."""
         _check(self.lib.he_apply_body_forces(self.h, None, None, _abi.SPACE_ENV, 1, self.stream))
+
+    # ------------------------------------------------------------------ torque control
+    def set_dof_drive_modes(self, modes):
+        """he_set_dof_drive_modes: one gymapi.DOF_MODE_* per dof ([69]; all envs share the articulation):
+        NONE 0, POS 1, EFFORT 3 (VEL 2 is refused). A dof that is not POS loses its PD drive; an EFFORT
+        dof takes the actuation forces. Clears any actuation that is set."""
+        m = np.ascontiguousarray(np.asarray(modes).reshape(-1), np.int32)
+        if m.shape != (_abi.ND,):
+            raise EngineError(f"dof drive modes: expected {_abi.ND} modes, got {m.shape[0]}")
+        _check(self.lib.he_set_dof_drive_modes(self.h, m.ctypes.data_as(C.c_void_p)))
+
+    def _actuation(self, t, what):
+        import torch
+        p = self._dev(t, torch.float32, what, self.num_envs * _abi.ND)
+        if tuple(t.shape) not in ((self.num_envs, _abi.ND), (self.num_envs * _abi.ND,)):
+            raise EngineError(f"{what} must be [num_envs,69] or [num_envs*69], got {tuple(t.shape)}")
+        return p
+
+    def set_dof_actuation_forces(self, t):
+        """gym.set_dof_actuation_force_tensor: joint torques [N,69] or [N*69] (N m, the engine's
+        child-frame joint coordinates). Applied on EFFORT dofs, clamped to the model's effort limits, in
+        every physics step until replaced or cleared (include/humanoid_engine.h)."""
+        _check(self.lib.he_set_dof_actuation_forces(self.h, self._actuation(t, "dof actuation forces"), self.stream))
+
+    def set_dof_actuation_forces_indexed(self, src, ids):
+        """Rows ``ids`` (int32 env ids) of the full-size ``src`` replace the actuation of those envs."""
+        import torch
+        p_src = self._actuation(src, "indexed actuation's full-size source")
+        p_ids = self._dev(ids, torch.int32, "indexed actuation's ids")
+        _check(self.lib.he_set_dof_actuation_forces_indexed(self.h, p_src, p_ids, int(ids.numel()), self.stream))
+
+    def clear_dof_actuation_forces(self):
+        """Drop the actuation: the next launch runs the kernels without it."""
+        _check(self.lib.he_set_dof_actuation_forces(self.h, None, self.stream))
 
     # ------------------------------------------------------------------ motion library
     def load_motions(self, tables):

@@ -16,6 +16,13 @@ Engine-specific behaviour (documented, not silent):
 * all envs share one articulation, PD gains and filter table (what puffer-phc does): a
   ``set_actor_dof_properties`` / ``set_actor_rigid_shape_properties`` that differs between envs
   raises ``NotImplementedError``;
+* torque control: ``set_actor_dof_properties`` takes ``DOF_MODE_POS``, ``DOF_MODE_EFFORT`` and
+  ``DOF_MODE_NONE`` per dof (the same for every env; ``DOF_MODE_VEL`` raises: there is no velocity
+  target tensor). A dof that is not POS has no PD drive; ``set_dof_actuation_force_tensor`` /
+  ``..._indexed`` put joint torques on the EFFORT dofs, clamped to the dofs' effort limits (the
+  engine's choice, as for the PD drive). The torques are in the coordinates of the dynamics tensors
+  below (``M qdd + c = (0_6, tau)``), and they stay set until the next write: callers that write them
+  before every ``simulate`` see Isaac Gym's behaviour whichever rule its binary follows;
 * no viewer (headless only: ``create_viewer`` raises), CPU pipeline refused (the engine is GPU-only);
 * camera SENSORS exist (``render_env.py:151-171, 218-227, 398-411``): ``create_camera_sensor``,
   ``set_camera_location`` / ``set_camera_transform`` / ``attach_camera_to_body``,
@@ -210,6 +217,7 @@ class Sim:
         self.asset: Asset | None = None
         self.plane: PlaneParams | None = None
         self.dof_props = None
+        self.dof_modes = None  # [69] gymapi.DOF_MODE_* once set_actor_dof_properties has been called
         self.shape_filters = None
         self.self_collision = None
         self.start_poses = []
@@ -322,12 +330,20 @@ class Gym:
 
     def set_actor_dof_properties(self, env: _Env, actor, props):
         sim = env.sim
-        if sim.dof_props is None:
+        modes = np.asarray(props["driveMode"], np.int32)
+        if np.any(modes == DOF_MODE_VEL):
+            raise NotImplementedError("DOF_MODE_VEL: the engine has no velocity target tensor "
+                                      "(DOF_MODE_POS, DOF_MODE_EFFORT and DOF_MODE_NONE exist)")
+        if not np.all(np.isin(modes, (DOF_MODE_NONE, DOF_MODE_POS, DOF_MODE_EFFORT))):
+            raise ValueError(f"driveMode outside gymapi.DOF_MODE_*: {sorted(set(modes.tolist()))}")
+        if sim.dof_props is not None:
+            if not all(np.array_equal(sim.dof_props[k], props[k]) for k in ("stiffness", "damping", "effort", "armature")):
+                raise NotImplementedError("per-env PD gains differ: the engine shares one articulation")
+            if not np.array_equal(sim.dof_modes, modes):
+                raise NotImplementedError("per-env drive modes differ: the engine shares one articulation")
+        else:
             sim.dof_props = np.array(props, copy=True)
-        elif not all(np.array_equal(sim.dof_props[k], props[k]) for k in ("stiffness", "damping", "effort", "armature")):
-            raise NotImplementedError("per-env PD gains differ: the engine shares one articulation")
-        if not np.all(np.asarray(props["driveMode"]) == DOF_MODE_POS):
-            raise NotImplementedError("only DOF_MODE_POS drives (control_mode isaac_pd)")
+            sim.dof_modes = modes.copy()
         return True
 
     def get_actor_rigid_shape_properties(self, env: _Env, actor):
@@ -379,6 +395,8 @@ class Gym:
         xy = np.array([p[0][:2] for p in sim.start_poses], np.float32)
         sim.engine = Engine(m, n, device=sim.device, sim_params=params, start_xy=xy)
         self._model = m
+        if sim.dof_modes is not None and np.any(sim.dof_modes != DOF_MODE_POS):
+            sim.engine.set_dof_drive_modes(sim.dof_modes)
         poses = np.array([list(p[0]) + list(p[1]) for p in sim.start_poses], np.float32)
         if not (np.allclose(poses[:, 2], 0.89) and np.allclose(poses[:, 3:7], [0, 0, 0, 1])):
             import torch
@@ -495,6 +513,20 @@ class Gym:
     def set_dof_position_target_tensor_indexed(self, sim: Sim, desc, ids_desc, n: int):
         self._flush(sim)
         sim.engine.set_dof_targets_indexed(self._tensor(desc), self._tensor(ids_desc)[:n])
+        return True
+
+    # -- torque control -------------------------------------------------------------------------------
+    def set_dof_actuation_force_tensor(self, sim: Sim, desc):
+        """Joint torques [N*69] (or [N,69]) on the DOF_MODE_EFFORT dofs, clamped to the dofs' effort
+        limits. The engine keeps them until the next write (``include/humanoid_engine.h``); written
+        before every ``simulate``, as every known caller does, that is Isaac Gym's behaviour."""
+        self._flush(sim)
+        sim.engine.set_dof_actuation_forces(self._tensor(desc))
+        return True
+
+    def set_dof_actuation_force_tensor_indexed(self, sim: Sim, desc, ids_desc, n: int):
+        self._flush(sim)
+        sim.engine.set_dof_actuation_forces_indexed(self._tensor(desc), self._tensor(ids_desc)[:n])
         return True
 
     # -- external forces (render_env.py:105-126) ------------------------------------------------------

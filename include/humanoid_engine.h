@@ -267,6 +267,40 @@ int he_apply_body_forces(he_engine* h, const float* force, const float* torque, 
 int he_apply_body_forces_at_pos(he_engine* h, const float* force, const float* pos, int space, int hold,
                                 void* stream);
 
+/* Torque control (gymapi.DOF_MODE_* of set_actor_dof_properties; gym.set_dof_actuation_force_tensor,
+ * the explicit-torque control mode of the reference's upstream and of every IsaacGymEnvs-style task).
+ *
+ * he_set_dof_drive_modes: host_modes [69], one mode per dof (all envs share one articulation, so the
+ * modes are per dof, not per env): 0 NONE, 1 POS, 3 EFFORT. 2 (VEL) is refused: the engine has no
+ * velocity-target tensor. Valid after he_set_model, before or after he_create_envs. The engine keeps
+ * the model's gains and re-uploads the device model with stiffness = damping = 0 on every dof that is
+ * not POS, so that dof's implicit PD drive yields no torque; the physics kernels are the same ones.
+ * All-POS is the state after he_set_model. The call clears any actuation that is set.
+ *
+ * he_set_dof_actuation_forces: src is a DEVICE array [N,69] of joint torques (N m), or NULL to clear.
+ * The engine keeps its own copy: on EFFORT dofs the source clamped to +-he_model.effort[d], on every
+ * other dof 0 (the clamp mirrors the PD drive's effort limit; it is this engine's choice, Isaac Gym
+ * documents none). The indexed form replaces rows ids[0..k) (int32 env ids) from a full-size source,
+ * like the other indexed writes; the other rows keep what they had (zero when nothing was set).
+ *   - The actuation is a setting, like the position targets: it persists over launches (he_simulate,
+ *     he_step_actions, he_env_step, every physics step of each) until it is replaced or cleared. A
+ *     reset does not touch it. Whether Isaac Gym's binary (not vendored) keeps or clears the tensor
+ *     after a step cannot be checked here; every known caller writes it before every gym.simulate(),
+ *     where the two rules coincide.
+ *   - The dof coordinate is the one include/humanoid_dynamics.h documents: the engine's child-frame
+ *     relative joint rates of the exp-map ball joints. With libhumanoid_dynamics' M (armature included)
+ *     and c, the step's acceleration satisfies M qdd + c = (0_6, tau).
+ *   - HE_BUF_DOF_FORCE includes the applied (clamped) actuation on EFFORT dofs.
+ * Nonzero (reason in he_last_error) for a null handle, modes before he_set_model, a mode outside
+ * {0, 1, 3}, or an actuation call without envs; a refused call changes nothing. */
+#define HE_DOF_MODE_NONE 0
+#define HE_DOF_MODE_POS 1
+#define HE_DOF_MODE_VEL 2
+#define HE_DOF_MODE_EFFORT 3
+int he_set_dof_drive_modes(he_engine* h, const int32_t* host_modes);
+int he_set_dof_actuation_forces(he_engine* h, const float* src, void* stream);
+int he_set_dof_actuation_forces_indexed(he_engine* h, const float* src, const int32_t* ids, int k, void* stream);
+
 /* ---------------- motion library + fused imitation kernel (A5-A9) ---------------------- */
 /* MotionLibBase.load_motions table upload (motion_lib.py:396-420). Host pointers; the engine
  * re-lays the frames out as interleaved per-frame records in device memory.
