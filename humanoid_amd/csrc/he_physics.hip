@@ -108,6 +108,32 @@ HE_DEV void sync() {
 
 HE_DEV int dof_body(int i) { return i < 6 ? 0 : (i - 6) / 3 + 1; }
 
+// A phase's own view of LDS and of the lane id, built from nothing that is live: an opaque zero
+// offset on the LDS window (substep's lds_off, taken again) and the lane from the wave's mbcnt (one
+// wave per workgroup: threadIdx.x). A per-lane LDS address formed from these is rebuilt beside its use
+// (one or two integer VALU) instead of being hoisted out of the position iterations as a loop
+// invariant, parked in scratch there and fetched back in front of the LDS read that needs it: a
+// memory round trip on the step's dependent path (spills). (The mbcnt pair as volatile
+// assembly: the builtins are merged with threadIdx.x's and hoisted like it.)
+HE_DEV Lds& phase_lds() {
+    extern __shared__ float smem[];
+    int off = 0;
+    asm volatile("" : "+v"(off));
+    return *reinterpret_cast<Lds*>(reinterpret_cast<char*>(smem) + off);
+}
+HE_DEV int phase_lane() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+// a wave-uniform value into an SGPR (SGPRs that run out are parked in VGPR lanes, a v_readlane away;
+// a uniform value left in a VGPR across the iterations is parked in scratch)
+HE_DEV float uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+HE_DEV int opaque_s(int x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+
 // optional per-phase cycle stamps (diagnostic: PhysArgs.stamps != null), lane 0 accumulates
 // s_memtime deltas per phase into stamps[block * HE_STAMP_SLOTS + phase] with a no-return vector
 // atomic add (a load-add-store would put one global round trip into every phase it opens)
@@ -1270,8 +1296,12 @@ HE_DEV void tgs_bias_at(Lds& L, const BodyTopo& T, int lane, const he_sim_params
     sync();
     __builtin_amdgcn_sched_barrier(0);
     subtree_levels<6, smpl::kNumBodyLevels - 2>(&L.Acc[0][0], nullptr, lane);
-    c1 = dot6(L.S[lane], L.Acc[dof_body(lane)]);
-    c2 = lanes_hi() ? dot6(L.S[64 + lane], L.Acc[(64 + lane - 6) / 3 + 1]) : 0.f;
+    // the dofs' S and Acc rows through the phase's own view: their six addresses are invariant over
+    // the iterations, and carried across them each came back from scratch in front of its read
+    const Lds& Lt = phase_lds();
+    const int ln = phase_lane();
+    c1 = dot6(Lt.S[ln], Lt.Acc[dof_body(ln)]);
+    c2 = lanes_hi() ? dot6(Lt.S[64 + ln], Lt.Acc[(64 + ln - 6) / 3 + 1]) : 0.f;
 }
 
 // the next position iteration's free motion: yh = D^-1/2 L^-T hs (kp (tgt - q) - c u - b) per dof (lane,
@@ -1311,7 +1341,10 @@ HE_DEV void tgs_velocity(Lds& L, const BodyTopo& T, int lane, float e1, float e2
 
 // the iteration's implicit drive torque kp (tgt - q) - c u at its end velocity, accumulated per dof
 // (lane, then 64 + lane): the reported drive force is the iterations' mean
-HE_DEV void tgs_drive_acc(const Lds& L, int lane, float& f1, float& f2) {
+HE_DEV void tgs_drive_acc(const Lds& L, int, float& f1, float& f2) {
+    // the lane afresh: max(lane, 6) below is the drive terms' own index at the step's start, and shared
+    // with it was parked in scratch through the rows' peak for this read
+    const int lane = phase_lane();
     auto tq = [&](int i) {
         const int d = i - 6;
         return L.dforce[d] * (L.tgt[d] - L.q[d]) - L.coef[i] * L.u0[i];
@@ -2071,6 +2104,14 @@ struct RowDesc {
     f3 dd, rho;    // the row's linear direction, and its moment about o (a torsional row: the normal)
     float lam0;    // the previous solve's impulse of the row's key
 };
+// The row's slot read again where a late phase needs it (row_setup's own read of rslot, which
+// build_rows wrote and nothing overwrites within the step): the slot's address held from the row
+// set-up through the rows' register peak came back from scratch in front of the gap's read.
+HE_DEV int row_slot_again(bool act) {
+    const Lds& L = phase_lds();
+    const int ln = phase_lane();
+    return act ? L.rslot[ln] : 0;
+}
 // Each row's Jacobian data: slot, kind, bodies; a friction row's patch (a body's terrain points
 // [tbase, tbase + tcnt), or the self pair alone) gives its tangent basis, centroid and torsion
 // radius. The warm start: the previous solve's impulse of each row's key (lane r matches its key
@@ -2173,7 +2214,7 @@ HE_DEV void row_system(Lds& L, const BodyTopo& T, const he_sim_params& p, bool f
     // row's support is there (the dropped terms are fma(0, u, s) = s: the same bits)
     s.brow = s.legs ? zdot_lds<KZ>(s.z, L.u0) : zdot_lds<NG>(s.z, L.u0);
     if (r.act && r.kind == 0) {
-        const float g = L.cgap[r.rs_];
+        const float g = L.cgap[row_slot_again(r.act)];
         // speculative: close within the solve's step; penetrating: recover at baumgarte per physics
         // step (TGS too: oracle contact_bias)
         s.brow += g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
@@ -2324,8 +2365,15 @@ struct TgsStep {
 // What follows a position iteration's velocity update: its drive torques, the positions by hs (the
 // last iteration: the step's output velocity), then (not the last) the next iteration's bias and
 // free motion
-template <bool EXT>
-HE_DEV void tgs_advance(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int it, TgsStep& ts, Stamps& st) {
+// WIDE (the 63-row class, whose columns leave no register for an address held over the iterations):
+// the phases' lane and LDS view taken afresh per iteration, so that the integration's, the bias
+// RNEA's and its subtree levels' per-lane addresses are rebuilt instead of fetched from scratch one
+// by one; the <= 32-row class and the free iterations keep theirs in registers.
+template <bool EXT, bool WIDE = false>
+HE_DEV void tgs_advance(Lds& L0, const BodyTopo& T0, const he_sim_params& p, int lane0, int it, TgsStep& ts, Stamps& st) {
+    Lds& L = WIDE ? phase_lds() : L0;
+    const BodyTopo& T = WIDE ? L.T : T0;
+    const int lane = WIDE ? phase_lane() : lane0;
     const bool lastit = it + 1 == ts.K;
     tgs_drive_acc(L, lane, ts.tf1, ts.tf2);
     integrate_bodies(L, T, lane, p, ts.hs, ts.damp, L.u0, lastit, lastit && !ts.last);
@@ -2355,8 +2403,11 @@ HE_DEV void tgs_advance(Lds& L, const BodyTopo& T, const he_sim_params& p, int l
 }
 // the reported drive force, the iterations' mean (the joint-limit force is added by the caller)
 HE_DEV void tgs_drive_out(Lds& L, int lane, const TgsStep& ts) {
-    if (lane >= 6) L.dforce[lane >= 6 ? lane - 6 : 0] = ts.tf1 / (float)ts.K;
-    if (lane < regla::NH) L.dforce[58 + lane] = ts.tf2 / (float)ts.K;
+    // the iteration count converted here, from its SGPR: (float)K held in a VGPR since the step's start
+    // was parked in scratch across the iterations and fetched back in front of each division
+    const float kf = (float)opaque_s(ts.K);
+    if (lane >= 6) L.dforce[lane >= 6 ? lane - 6 : 0] = ts.tf1 / kf;
+    if (lane < regla::NH) L.dforce[58 + lane] = ts.tf2 / kf;
     sync();
 }
 
@@ -2399,7 +2450,7 @@ HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int la
         return g >= 0.f ? g / hs : fmaxf(p.baumgarte * g / dt, -p.max_depenetration_velocity);
     };
     const float kInf = __builtin_inff();
-    float sep = act && isn ? L.cgap[r.rs_] : 0.f;  // the row's separation (a limit row: its angle gap)
+    float sep = act && isn ? L.cgap[row_slot_again(act)] : 0.f;  // the row's separation (a limit row: its angle gap)
     float bb = act && isn ? gbias(sep) : 0.f;     // its bias (brow holds it)
     float applied = 0.f;                           // the impulse already in the working velocity
     float lamv = g0;
@@ -2445,7 +2496,7 @@ HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int la
         STAMP(PH_DU_SOLVE);
         if (isn) sep += hs * v;
         const bool lastit = it + 1 == ts.K;
-        tgs_advance<EXT>(L, T, p, lane, it, ts, st);
+        tgs_advance<EXT, (NC > 32)>(L, T, p, lane, it, ts, st);
         __builtin_amdgcn_sched_barrier(0);
         if (!lastit) {
             // the next sweep's start about lambda = applied + dl: w = J u + zh . yh + bias(sep) + A dl,
@@ -2477,7 +2528,7 @@ template <bool EXT>
 HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
                             const RowSystem& s, TgsStep& ts, Stamps& st) {
     const int nrb = __builtin_amdgcn_readfirstlane(nr);
-    const float g0 = r.lam0 * (1.0f / (float)ts.K);
+    const float g0 = r.lam0 * (1.0f / (float)opaque_s(ts.K));  // K from its SGPR (tgs_drive_out)
     float w0 = s.brow;
     if (__ballot(g0 != 0.f)) w0 += warm_residual(s.acol, g0, nrb);  // wave-uniform
     float lamv;
@@ -2608,7 +2659,8 @@ HE_DEV void pgs_drive_out(Lds& L, int lane, int nr, float dt) {
 // Reported contact forces (net linear contact impulse per body / dt), lane = body: the output is the
 // last substep's, so the earlier substeps skip them (their cf rows stay zero, as gen_contacts set
 // them). Turns row_dirs into the per-row linear impulses (the stored directions x lambda).
-HE_DEV void contact_forces_out(Lds& L, int lane, int nc, bool act, float lamv, float dt) {
+HE_DEV void contact_forces_out(Lds&, int lane, int nc, bool act, float lamv, float dt) {
+    Lds& L = phase_lds();  // the step's LDS base does not survive the iterations in a register
     float* fr = row_dirs(L);
     if (act) {
         fr[3 * lane] *= lamv;
@@ -2665,15 +2717,18 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     asm volatile("" : "+v"(lds_off));
     Lds& L = *reinterpret_cast<Lds*>(reinterpret_cast<char*>(&L0) + lds_off);
     // and the lane id: the many per-lane predicates of the unrolled algebra are then rebuilt
-    // next to their use instead of being hoisted as loop invariants
-    asm volatile("" : "+v"(lane));
+    // next to their use instead of being hoisted as loop invariants (TGS: taken afresh, so that the
+    // kernel's own copy does not wait in scratch for the next substep's entry)
+    if constexpr (TGS) lane = phase_lane();
+    else asm volatile("" : "+v"(lane));
     const BodyTopo& T = L.T;
     const he_sim_params& p = a.p;
     const float dt = p.dt;
     // TGS (solver_type 1, oracle substep_tgs): K position iterations of hs = dt / K on this step's
     // factor and contact set; PGS: one step of hs = dt
     const int K = TGS ? (p.solver_iterations < 1 ? 1 : (p.solver_iterations > kTgsMaxIt ? kTgsMaxIt : p.solver_iterations)) : 1;
-    const float hs = TGS ? dt / (float)K : dt;
+    // TGS: hs (and damp below) in SGPRs, so that neither is a VGPR value parked across the iterations
+    const float hs = TGS ? uniform(dt / (float)K) : dt;
     __builtin_amdgcn_s_setprio(kPrioDefault);
     kinematics<true>(L, m, lane, a.p, !first);
     __builtin_amdgcn_s_setprio(kPrioDefault);
@@ -2701,7 +2756,7 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     STAMP(PH_CONTACT_GEN);
     RowDesc rd;
     row_setup(L, lane, nr, mu, lam_prev, rd);
-    const float damp = 1.0f / (1.0f + dt * p.angular_damping);
+    const float damp = TGS ? uniform(1.0f / (1.0f + dt * p.angular_damping)) : 1.0f / (1.0f + dt * p.angular_damping);
     TgsStep ts{K, hs, damp, last, 0.f, 0.f};
     if (nr > 0) {
         RowSystem rsys;
@@ -2875,7 +2930,7 @@ HE_DEV void physics_body(const PhysArgs& a) {
     extern __shared__ float smem[];
     Lds& L = *reinterpret_cast<Lds*>(smem);
     if ((int)blockIdx.x >= a.num_envs) return;  // the first-dispatch warm-up (warm_physics_kernels): no env
-    const int lane = threadIdx.x;
+    int lane = threadIdx.x;
     // the env of this workgroup (launch_physics_order: heavy envs first); it and the start cycle wait
     // in LDS for the epilogue (no registers held through the substeps)
     // The order is rebuilt on the launch stream (he_engine.cpp); an index outside [0, num_envs) (a
@@ -2886,10 +2941,11 @@ HE_DEV void physics_body(const PhysArgs& a) {
         L.sch_t0 = __builtin_readcyclecounter();
         L.sch_e = e;
     }
-    // ---- tables, state, warm-start cache
-    load_tables(L, a, lane);
-    load_state(L, a, e, lane);
-    cache_load(L, a, e, lane);
+    // ---- tables, state, warm-start cache (TGS: each with a lane of its own, a short live range)
+    load_tables(L, a, TGS ? phase_lane() : lane);
+    load_state(L, a, e, TGS ? phase_lane() : lane);
+    cache_load(L, a, e, TGS ? phase_lane() : lane);
+    if constexpr (TGS) lane = phase_lane();
     if (a.fused && lane == 0) {  // fused imitation: bookkeeping + motion metadata (trips 1, 2) now
         const ImitArgs& im = a.im;
         const int64_t mid = clamp_mid(im.m, im.motion_ids[e]);
@@ -2906,7 +2962,8 @@ HE_DEV void physics_body(const PhysArgs& a) {
         sync();
     }
     const float* ms = a.mass_scale ? a.mass_scale + (size_t)e * NB : nullptr;
-    float mu = a.friction ? a.friction[e] : a.p.friction;
+    // wave-uniform, into an SGPR: in a VGPR it is parked in scratch from one row set-up to the next
+    const float mu = uniform(a.friction ? a.friction[e] : a.p.friction);
     int tk = (a.p.terrain && a.terrain_kind) ? a.terrain_kind[e] : 0;
     Stamps st{a.stamps ? a.stamps + (size_t)e * HE_STAMP_SLOTS : nullptr, __builtin_readcyclecounter()};
     // ---- substeps
@@ -2918,6 +2975,9 @@ HE_DEV void physics_body(const PhysArgs& a) {
         const bool first = EXT ? s == 0 || s == a.ext_steps : s == 0;
         substep<TGS, EXT>(L, a, a.model, lane, ms, mu, tk, st, first, s == a.substeps - 1, EXT && s < a.ext_steps);
     }
+    // TGS: the epilogue's lane taken afresh, so that no address the prologue formed from the lane waits
+    // in scratch through the substeps for the epilogue
+    if constexpr (TGS) lane = phase_lane();
     // ---- fused imitation (he_env_step): the reference samples depend only on the env's motion
     // bookkeeping (read into LDS at the kernel's start), so their loads are issued here and land
     // behind the final kinematics and stores
