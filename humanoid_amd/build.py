@@ -1,6 +1,7 @@
 """Build ``humanoid_amd/libhumanoid_engine.so`` (with its diagnostic twin), the camera-sensor
-library ``humanoid_amd/libhumanoid_render.so`` and the dynamics-query library
-``humanoid_amd/libhumanoid_dynamics.so`` for gfx950 with hipcc (in-tree, they travel with the
+library ``humanoid_amd/libhumanoid_render.so``, the dynamics-query library
+``humanoid_amd/libhumanoid_dynamics.so`` and the joint-space solve library
+``humanoid_amd/libhumanoid_solve.so`` for gfx950 with hipcc (in-tree, they travel with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
 import hashlib
 import os
@@ -23,6 +24,12 @@ RENDER_SOURCES = [("hr_render.hip", [])]
 # a library of its own that only reads the engine's state buffers
 DYNAMICS_LIB = os.path.join(HERE, "libhumanoid_dynamics.so")
 DYNAMICS_SOURCES = [("hd_dynamics.hip", [])]
+# the joint-space solves (include/humanoid_solve.h: forward dynamics, computed torque, M^-1 on a block of
+# vectors): a fourth library, which reads the engine's state buffers and includes the engine's
+# register algebra (he_regla.h) without being linked into it
+SOLVE_LIB = os.path.join(HERE, "libhumanoid_solve.so")
+# no SLP vectorisation, as for the physics kernel: the elimination issues its packed FMAs itself
+SOLVE_SOURCES = [("hs_solve.hip", ["-fno-slp-vectorize"])]
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("HE_OFFLOAD_ARCH", "gfx950")
 
@@ -45,7 +52,8 @@ SOURCES = [
 HEADERS = ["he_host.h", "he_kernels.h", "he_math.h", "he_imitation_env.h", "he_topo.h", "he_regla.h", "he_smpl_topo.h", os.path.join("..", "..", "include", "humanoid_engine.h"),
            os.path.join("..", "..", "include", "humanoid_rollout.h"),
            os.path.join("..", "..", "include", "humanoid_render.h"),
-           os.path.join("..", "..", "include", "humanoid_dynamics.h")]
+           os.path.join("..", "..", "include", "humanoid_dynamics.h"),
+           os.path.join("..", "..", "include", "humanoid_solve.h")]
 
 
 def _hipcc():
@@ -67,8 +75,10 @@ MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2)}
 MIN_KERNELS = {"he_physics.hip": 2}
 # kernels that must not touch scratch memory (no spilled registers, no stack): the render kernel keeps
 # its primitives in LDS and everything else in registers; the dynamics kernel keeps its matrices in
-# named registers and indexes only LDS
-NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_kernel"}
+# named registers and indexes only LDS; the solve kernels (a source names one kernel or a tuple of
+# them) hold the mass matrix and its factorisation in registers, within the 256 of two waves per SIMD
+NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_kernel",
+              "hs_solve.hip": ("solve_kernel", "torque_kernel")}
 # ceilings on the physics kernels' register spills, by exact kernel name: (scratch bytes per lane,
 # spilled VGPRs) of the compiler's resource report, no slack (as the occupancy). The TGS kernel's
 # spills are a plan, not a by-product: what is parked is the <= 32-row class's columns
@@ -81,10 +91,14 @@ MAX_SPILLS = {"he_physics.hip": {"physics_kernel_tgs": (148, 36), "physics_kerne
 
 
 def _check_scratch(src, stderr):
-    name = NO_SCRATCH.get(os.path.basename(src))
-    if not name:
+    names = NO_SCRATCH.get(os.path.basename(src))
+    if not names:
         return
-    lines = stderr.splitlines()
+    for name in (names,) if isinstance(names, str) else names:
+        _check_kernel_scratch(name, stderr.splitlines())
+
+
+def _check_kernel_scratch(name, lines):
     for i, ln in enumerate(lines):
         if "Function Name:" in ln and name in ln:
             for ln2 in lines[i + 1:]:
@@ -215,7 +229,7 @@ def build(force=False, verbose=False):
             _compile(hipcc, cmd, s, o, force and lib == LIB or force and src in defs, hdr_time, verbose,
                      product=src not in defs)
         _link(hipcc, lib, objs, force)
-    for lib, sources in ((RENDER_LIB, RENDER_SOURCES), (DYNAMICS_LIB, DYNAMICS_SOURCES)):
+    for lib, sources in ((RENDER_LIB, RENDER_SOURCES), (DYNAMICS_LIB, DYNAMICS_SOURCES), (SOLVE_LIB, SOLVE_SOURCES)):
         objs = []
         for src, flags in sources:
             s = os.path.join(CSRC, src)

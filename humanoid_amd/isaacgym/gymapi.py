@@ -38,7 +38,11 @@ Engine-specific behaviour (documented, not silent):
   (root linear 3, root angular 3, the 69 dofs); the dof columns refer to the engine's child-frame
   relative rates of the exp-map ball joints, and the mass matrix carries the dof armature, as the
   engine's own solve does. ENGINE EXTENSION (not in Isaac Gym): ``acquire_bias_force_tensor`` [N,75]
-  / ``refresh_bias_force_tensors``, the gravity + Coriolis force c of ``M qdd + c = tau``.
+  / ``refresh_bias_force_tensors``, the gravity + Coriolis force c of ``M qdd + c = tau``;
+* ENGINE EXTENSION: the solves with that ``M``, each one HIP launch from the current state with ``M``
+  kept in registers (``include/humanoid_solve.h``): ``solve_forward_dynamics`` (``qdd = M^-1 (f - c)``),
+  ``solve_computed_torque`` (joint torques and base acceleration for desired joint accelerations) and
+  ``solve_mass_matrix`` (``M^-1`` on up to 32 rows per env, e.g. a Jacobian block).
 """
 from __future__ import annotations
 
@@ -475,6 +479,39 @@ class Gym:
 
     def refresh_bias_force_tensors(self, sim: Sim):
         return self._refresh_dynamics(sim, "bias")
+
+    # -- the solves with M (engine extensions) ------------------------------------------------------
+    def _solve_dynamics(self, sim: Sim, what: str):
+        if sim.engine is None:
+            raise RuntimeError(f"{what} before prepare_sim")
+        self._flush(sim)  # the solve sees the state after every simulate call so far
+        if sim.dynamics is None:
+            from ..dynamics import Dynamics
+            sim.dynamics = Dynamics(sim.engine)
+        return sim.dynamics
+
+    def solve_forward_dynamics(self, sim: Sim, gen_force_desc, out_desc):
+        """Engine extension: out [N,75] = M^-1 (gen_force - c) at the current state; ``gen_force_desc``
+        [N,75] or None for zero."""
+        dyn = self._solve_dynamics(sim, "solve_forward_dynamics")
+        dyn.forward_dynamics(None if gen_force_desc is None else self._tensor(gen_force_desc), self._tensor(out_desc))
+        return True
+
+    def solve_computed_torque(self, sim: Sim, qdd_des_desc, tau_out_desc, base_acc_desc=None):
+        """Engine extension: tau [N,69] (and the base acceleration [N,6] when asked) for the desired joint
+        accelerations qdd_des [N,69]: M (a_b; qdd_des) + c = (0_6; tau). The torques are not clamped;
+        ``set_dof_actuation_force_tensor`` clamps to the effort limits when they are applied."""
+        dyn = self._solve_dynamics(sim, "solve_computed_torque")
+        dyn.solver.computed_torque(self._tensor(qdd_des_desc), None, self._tensor(tau_out_desc),
+                                   None if base_acc_desc is None else self._tensor(base_acc_desc),
+                                   want_base_acc=base_acc_desc is not None)
+        return True
+
+    def solve_mass_matrix(self, sim: Sim, rhs_desc, out_desc):
+        """Engine extension: out [N,k,75] = M^-1 on each of the k <= 32 rows of rhs [N,k,75]."""
+        dyn = self._solve_dynamics(sim, "solve_mass_matrix")
+        dyn.solve(self._tensor(rhs_desc), self._tensor(out_desc))
+        return True
 
     def _flush(self, sim: Sim):
         if sim.pending_substeps:
