@@ -585,6 +585,10 @@ int he_load_motions(he_engine* h, int64_t F, int M, const float* gts, const floa
         if (num_frames[i] < 1 || length_starts[i] < 0 || length_starts[i] + num_frames[i] > F)
             return fail("he_load_motions: motion %d frames [%lld, +%lld) outside the %lld-frame table", i,
                         (long long)length_starts[i], (long long)num_frames[i], (long long)F);
+        // a one-frame motion has length 0: its sampling phase is 0/0 (and the reference cannot load one)
+        if (num_frames[i] < 2)
+            return fail("he_load_motions: motion %d has %lld frame(s), a motion needs at least 2", i,
+                        (long long)num_frames[i]);
     }
     HE_CHECK(hipSetDevice(h->device));
     const int B = HE_NUM_BODIES;
@@ -614,7 +618,7 @@ int he_load_motions(he_engine* h, int64_t F, int M, const float* gts, const floa
     return 0;
 }
 
-int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames, const float* host_fps,
+int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames, const double* host_fps,
                     const float* pose_quat_global, const float* root_trans, int num_motions,
                     const int32_t* host_motion_clip, void* stream) {
     if (!h) return fail("he_ingest_clips: null handle");
@@ -628,12 +632,16 @@ int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames,
     std::vector<float> cdt(num_clips);
     int64_t F = 0;
     for (int c = 0; c < num_clips; ++c) {
-        if (host_num_frames[c] < 1 || !(host_fps[c] > 0.f))
+        // a one-frame clip has length 0: its sampling phase is 0/0 (and the reference cannot load one)
+        if (host_num_frames[c] < 2)
+            return fail("he_ingest_clips: clip %d has %lld frame(s), a clip needs at least 2", c,
+                        (long long)host_num_frames[c]);
+        if (!(host_fps[c] > 0.0) || !std::isfinite(host_fps[c]))  // NaN fails the first test
             return fail("he_ingest_clips: clip %d has %lld frames at %g fps", c, (long long)host_num_frames[c],
-                        (double)host_fps[c]);
+                        host_fps[c]);
         cstart[c] = F;
         cnf[c] = host_num_frames[c];
-        cdt[c] = (float)(1.0 / (double)host_fps[c]);
+        cdt[c] = (float)(1.0 / host_fps[c]);
         F += host_num_frames[c];
     }
     std::vector<int64_t> ms(num_motions), mn(num_motions);
@@ -644,8 +652,8 @@ int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames,
         ms[i] = cstart[c];
         mn[i] = cnf[c];
         // motion_lib.py:376-379: curr_len = 1/fps * (num_frames - 1) in python floats -> float32
-        ml[i] = (float)(1.0 / (double)host_fps[c] * (double)(cnf[c] - 1));
-        mdt[i] = (float)(1.0 / (double)host_fps[c]);
+        ml[i] = (float)(1.0 / host_fps[c] * (double)(cnf[c] - 1));
+        mdt[i] = (float)(1.0 / host_fps[c]);
     }
     HE_CHECK(hipSetDevice(h->device));
     const hipStream_t st = (hipStream_t)stream;

@@ -3,7 +3,8 @@
 // host path MotionLibSMPL.load_motion_with_skeleton (motion_lib.py:743-824) + the poselib
 // SkeletonState / SkeletonMotion construction (poselib_skeleton.py:518-539, 574-592, 1166-1251)
 // + compute_motion_dof_vels_jit (motion_lib.py:119-140). Restated on the host in
-// humanoid_amd/motion_lib.py:clip_to_motion, which the GPU tests use as the checker.
+// humanoid_amd/motion_lib.py:clip_to_motion; the GPU tests check both against an independent
+// float64 ingestion (tests/ingest_reference.py) frame by frame.
 //
 // Two launches over all frames of all clips (one 32-lane group per frame, lane = body):
 //   1. frame_kernel: local rotations, FK translations, raw angular velocity (successive global

@@ -332,7 +332,11 @@ class Engine:
         library motion i uses clip ``motion_clip[i]`` (default: one motion per clip)."""
         import torch
         nf = np.array([len(c["pose_quat_global"]) for c in clips], np.int64)
-        fps = np.array([float(c.get("fps", 30)) for c in clips], np.float32)
+        # float64: dt and length are 1 / fps in Python floats, rounded to float32 afterwards (the reference)
+        fps = np.array([float(c.get("fps", 30)) for c in clips], np.float64)
+        for i, c in enumerate(clips):  # per clip: two mismatches can cancel in the concatenation
+            if len(c["root_trans_offset"]) != nf[i]:
+                raise EngineError(f"clip {i} has {nf[i]} pose frames and {len(c['root_trans_offset'])} translations")
         pose = torch.as_tensor(np.concatenate([np.asarray(c["pose_quat_global"], np.float32) for c in clips], 0))
         trans = torch.as_tensor(np.concatenate([np.asarray(c["root_trans_offset"], np.float32).reshape(-1, 3)
                                                 for c in clips], 0))

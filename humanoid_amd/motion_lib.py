@@ -58,7 +58,7 @@ def clip_to_motion(model: HumanoidModel, clip: dict) -> Dict[str, np.ndarray]:
     """One clip -> per-frame tables (numpy restatement of the poselib path, float32 math)."""
     grs = np.asarray(clip["pose_quat_global"], np.float32)
     trans = np.asarray(clip["root_trans_offset"], np.float32)
-    fps = int(clip.get("fps", 30))
+    fps = clip.get("fps", 30)  # as given (motion_lib.py:375-379, 813-815): 59.94 stays 59.94
     T, B = grs.shape[:2]
     parents = model.parents
     # local rotations (poselib_skeleton.py:574-592)
@@ -182,13 +182,13 @@ class MotionLibSMPL:
         uniq, inv = np.unique(idx, return_inverse=True)
         clips = [self._motion_data_list[i] for i in uniq]
         nf = np.array([len(c["pose_quat_global"]) for c in clips], np.int64)[inv]
-        fps = np.array([int(c.get("fps", 30)) for c in clips], np.int64)[inv]
+        fps = np.array([float(c.get("fps", 30)) for c in clips], np.float64)[inv]
         # motion_lib.py:376-379 (python floats -> float32)
-        lengths = np.array([1.0 / int(f) * (int(k) - 1) for f, k in zip(fps, nf)], np.float32)
+        lengths = np.array([1.0 / float(f) * (int(k) - 1) for f, k in zip(fps, nf)], np.float32)
         self._motion_lengths = torch.as_tensor(lengths, device=self._device)
         self._motion_num_frames = torch.as_tensor(nf, device=self._device)
         self._motion_fps = torch.as_tensor(fps.astype(np.float32), device=self._device)
-        self._motion_dt = torch.as_tensor(np.array([1.0 / int(f) for f in fps], np.float32), device=self._device)
+        self._motion_dt = torch.as_tensor(np.array([1.0 / float(f) for f in fps], np.float32), device=self._device)
         self._num_loaded = int(num_motion_to_load)
         return clips, inv.astype(np.int32)
 

@@ -304,7 +304,9 @@ int he_set_dof_actuation_forces_indexed(he_engine* h, const float* src, const in
 /* ---------------- motion library + fused imitation kernel (A5-A9) ---------------------- */
 /* MotionLibBase.load_motions table upload (motion_lib.py:396-420). Host pointers; the engine
  * re-lays the frames out as interleaved per-frame records in device memory.
- * gts/gvs/gavs [F,24,3], grs/lrs [F,24,4], dvs [F,23,3]; per-motion arrays [M]. */
+ * gts/gvs/gavs [F,24,3], grs/lrs [F,24,4], dvs [F,23,3]; per-motion arrays [M]. A motion needs at
+ * least 2 frames (a one-frame motion has length 0 and cannot be sampled; the reference cannot load
+ * one either): such a table is refused, and a refused call leaves the loaded library in place. */
 int he_load_motions(he_engine* h, int64_t num_frames_total, int num_motions,
                     const float* gts, const float* grs, const float* lrs, const float* gvs,
                     const float* gavs, const float* dvs, const int64_t* length_starts,
@@ -318,8 +320,12 @@ int he_load_motions(he_engine* h, int64_t num_frames_total, int num_motions,
  * the motion tables on the device (local rotations, FK translations, Gaussian-filtered linear and
  * angular velocities, dof velocities). Motion i of the library refers to clip
  * host_motion_clip[i] (HOST, [num_motions]; NULL = identity with num_motions = num_clips), as the
- * reference's per-env motion entries share clips. Synchronises `stream`. */
-int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames, const float* host_fps,
+ * reference's per-env motion entries share clips. Synchronises `stream`.
+ * host_fps is double: the reference computes dt = 1 / fps and length = 1 / fps * (frames - 1) in
+ * Python floats and only then rounds to float32, so a fractional rate (59.94) must arrive unrounded.
+ * Refused (nonzero, reason in he_last_error, the loaded library left in place): a clip of fewer than
+ * 2 frames, an fps that is not a positive finite number, a motion->clip entry out of range. */
+int he_ingest_clips(he_engine* h, int num_clips, const int64_t* host_num_frames, const double* host_fps,
                     const float* pose_quat_global, const float* root_trans, int num_motions,
                     const int32_t* host_motion_clip, void* stream);
 
