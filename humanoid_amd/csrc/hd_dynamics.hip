@@ -1,5 +1,6 @@
 // libhumanoid_dynamics.so: body Jacobians, joint-space inertia and bias force of every env
 // (include/humanoid_dynamics.h defines the three). One launch, one 64-lane wave (= one block) per env:
+// (load and kinematics are he_tree_state.h's tree_kinematics, shared with hs_solve.hip)
 //   load       root row and the 69 (pos, vel) pairs into LDS;
 //   kinematics lanes 0..23 take one body each: the joint's Rodrigues matrix in registers, then one
 //              pass per tree level composes rotation, origin (relative to the root origin o = p_0, the
@@ -17,42 +18,22 @@
 //              origins; both are exact zeros off the tree's pattern.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <memory>
 
 #include "../../include/humanoid_dynamics.h"
 #include "he_host.h"
 #include "he_topo.h"
+#include "he_tree_state.h"
 
 namespace {
 
-constexpr int NB = HE_NUM_BODIES;
-constexpr int ND = HE_NUM_DOF;
-constexpr int NG = HE_NUM_GEN;
-constexpr int kWave = 64;
 constexpr int kJacEnv = NB * HD_JAC_ROWS * NG;  // 10800 dwords per env
 constexpr int kJacBody = HD_JAC_ROWS * NG;      // 450
 constexpr int kMassEnv = NG * NG;               // 5625
-constexpr int kMaxDepth = 8;                    // joints on the longest chain (he_topo.h body_chain)
-
-// what the kernel reads of the model (hd_create)
-struct DModel {
-    int32_t parent[NB];
-    int32_t depth[NB];
-    uint32_t anc[NB];  // bit a: a is ancestor-or-self of b
-    uint32_t sub[NB];  // bit d: d in subtree(b)
-    float local_pos[NB][3];
-    float mass[NB];
-    float com[NB][3];
-    float inertia[NB][6];  // xx yy zz xy xz yz
-    float armature[ND];
-    float gravity[3];
-    int32_t max_depth;
-};
 
 struct Params {
-    const DModel* model;
+    const TreeModel* model;
     const float* root;  // [N,13]
     const float* dof;   // [N*69,2]
     float* jac;         // [N,24,6,75] or null
@@ -60,73 +41,6 @@ struct Params {
     float* bias;        // [N,75] or null
     uint32_t flags;
 };
-
-struct v3 {
-    float x, y, z;
-};
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ v3 operator*(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-// S . F = w . n + v . p in one fixed order of fused multiply-adds
-__device__ __forceinline__ float dot6(v3 w, v3 v, v3 n, v3 p) {
-    return fmaf(v.z, p.z, fmaf(v.y, p.y, fmaf(v.x, p.x, fmaf(w.z, n.z, fmaf(w.y, n.y, w.x * n.x)))));
-}
-__device__ __forceinline__ v3 ld3(const float* p) { return v3{p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st3(float* p, v3 a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
-
-// a 3x3 matrix in named registers (row-major): no indexed register arrays, so nothing goes to scratch
-struct m3 {
-    float a00, a01, a02, a10, a11, a12, a20, a21, a22;
-};
-__device__ __forceinline__ v3 mul(const m3& m, v3 v) {
-    return v3{m.a00 * v.x + m.a01 * v.y + m.a02 * v.z, m.a10 * v.x + m.a11 * v.y + m.a12 * v.z,
-              m.a20 * v.x + m.a21 * v.y + m.a22 * v.z};
-}
-__device__ __forceinline__ m3 mul(const m3& a, const m3& b) {
-    return m3{a.a00 * b.a00 + a.a01 * b.a10 + a.a02 * b.a20, a.a00 * b.a01 + a.a01 * b.a11 + a.a02 * b.a21,
-              a.a00 * b.a02 + a.a01 * b.a12 + a.a02 * b.a22, a.a10 * b.a00 + a.a11 * b.a10 + a.a12 * b.a20,
-              a.a10 * b.a01 + a.a11 * b.a11 + a.a12 * b.a21, a.a10 * b.a02 + a.a11 * b.a12 + a.a12 * b.a22,
-              a.a20 * b.a00 + a.a21 * b.a10 + a.a22 * b.a20, a.a20 * b.a01 + a.a21 * b.a11 + a.a22 * b.a21,
-              a.a20 * b.a02 + a.a21 * b.a12 + a.a22 * b.a22};
-}
-__device__ __forceinline__ m3 ldm(const float* p) { return m3{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]}; }
-__device__ __forceinline__ void stm(float* p, const m3& m) {
-    p[0] = m.a00, p[1] = m.a01, p[2] = m.a02, p[3] = m.a10, p[4] = m.a11, p[5] = m.a12, p[6] = m.a20, p[7] = m.a21,
-    p[8] = m.a22;
-}
-
-// exp([v]x) = 1 + A K + B K^2, A = sin(th) / th, B = (1 - cos th) / th^2 = 2 sin^2(th / 2) / th^2 (no
-// cancellation); below 1e-3 rad the series (the next terms are under 1e-14)
-__device__ __forceinline__ m3 rodrigues(v3 v) {
-    const float t2 = dot(v, v);
-    float A, B;
-    if (t2 < 1e-6f) {
-        A = 1.f - t2 * (1.f / 6.f);
-        B = 0.5f - t2 * (1.f / 24.f);
-    } else {
-        const float th = sqrtf(t2);
-        const float sh = sinf(0.5f * th);
-        A = sinf(th) / th;
-        B = 2.f * sh * sh / t2;
-    }
-    const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z;
-    const float xy = B * v.x * v.y, xz = B * v.x * v.z, yz = B * v.y * v.z;
-    return m3{1.f - B * (yy + zz), xy - A * v.z, xz + A * v.y, xy + A * v.z, 1.f - B * (xx + zz), yz - A * v.x,
-              xz - A * v.y, yz + A * v.x, 1.f - B * (xx + yy)};
-}
-
-__device__ __forceinline__ m3 quat_matrix(float x, float y, float z, float w) {
-    const float n2 = x * x + y * y + z * z + w * w;
-    if (n2 < 1e-24f) return m3{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    const float s = 2.f / n2;
-    return m3{1.f - s * (y * y + z * z), s * (x * y - z * w), s * (x * z + y * w), s * (x * y + z * w),
-              1.f - s * (x * x + z * z), s * (y * z - x * w), s * (x * z - y * w), s * (y * z + x * w),
-              1.f - s * (x * x + y * y)};
-}
-
-__device__ __forceinline__ int col_joint(int c) { return c < 6 ? 0 : 1 + (c - 6) / 3; }
 
 // a column of the mass matrix: S = (w, v), F = I^c S = (n, p), its joint and the joint's ancestor mask
 struct Col {
@@ -155,13 +69,11 @@ __device__ __forceinline__ float mass_entry(int i, int k, const Col& ci, const C
     return val;
 }
 
-__global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
-    __shared__ float sQ[ND], sU[ND];
-    __shared__ float sR[NB][9];   // world rotation, row-major
-    __shared__ float sP[NB][3];   // origin relative to the root origin o
-    __shared__ float sW[NB][3];   // world angular velocity
-    __shared__ float sWd[NB][3];  // world angular acceleration at qdd = 0
-    __shared__ float sA[NB][3];   // origin acceleration at qdd = 0
+// 4 waves per SIMD is what a grid of 4096 envs fills (16 blocks per CU); saying so gives the register
+// allocator 128 VGPRs to schedule the serial prologue with
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 4))) void dynamics_kernel(const Params P) {
+    // the kinematic state at qdd = 0, one array each (he_tree_state.h names them and says why)
+    __shared__ float sQ[ND], sU[ND], sR[NB][9], sP[NB][3], sW[NB][3], sWd[NB][3], sA[NB][3];
     __shared__ float sBody[NB][16];  // about o: m, h3 = m c, I_o (xx yy zz xy xz yz), wrench (n3, f3)
     __shared__ float sComp[NB][16];  // the same summed over the body's subtree
     __shared__ __align__(16) float sSF[NG][12];  // per column: motion vector S (w, v_o), then F = I^c S (n_o, p)
@@ -169,84 +81,36 @@ __global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
 
     const int lane = threadIdx.x;
     const size_t env = blockIdx.x;
-    const DModel& M = *P.model;
+    const TreeModel& M = *P.model;
+    const TreeState S{sQ, sU, nullptr, sR, sP, sW, sWd, sA};
 
-    for (int d = lane; d < ND; d += kWave) {
-        const float* row = P.dof + (env * ND + d) * 2;
-        sQ[d] = row[0];
-        sU[d] = row[1];
-    }
-    const float* root = P.root + env * 13;
-    m3 Rl{};  // body b >= 1: the joint's rotation; filled after the barrier below
-    int depth = -1, parent = 0;
-    if (lane < NB) {
-        depth = M.depth[lane];
-        parent = M.parent[lane];
-        sAnc[lane] = M.anc[lane];
-        if (lane == 0) {
-            stm(sR[0], quat_matrix(root[3], root[4], root[5], root[6]));
-            st3(sP[0], v3{0.f, 0.f, 0.f});
-            st3(sW[0], ld3(root + 10));
-            st3(sWd[0], v3{0.f, 0.f, 0.f});
-            st3(sA[0], v3{0.f, 0.f, 0.f});
-        }
-    }
-    __syncthreads();
-    if (lane >= 1 && lane < NB) Rl = rodrigues(ld3(&sQ[3 * (lane - 1)]));
-
-    // one pass per tree level (max_depth is the model's: the same in every lane)
-    const int levels = M.max_depth;
-    for (int lvl = 1; lvl <= levels; ++lvl) {
-        if (depth == lvl) {
-            const int b = lane, a = parent;
-            const m3 Ra = ldm(sR[a]);
-            const v3 wa = ld3(sW[a]), wda = ld3(sWd[a]);
-            const m3 Rb = mul(Ra, Rl);
-            const v3 d = mul(Ra, ld3(M.local_pos[b]));
-            const v3 wrel = mul(Rb, ld3(&sU[3 * (b - 1)]));
-            stm(sR[b], Rb);
-            st3(sP[b], ld3(sP[a]) + d);
-            st3(sW[b], wa + wrel);
-            st3(sWd[b], wda + cross(wa, wrel));
-            st3(sA[b], ld3(sA[a]) + cross(wda, d) + cross(wa, cross(wa, d)));
-        }
-        __syncthreads();
-    }
+    tree_kinematics<false>(S, P.model, P.root, P.dof, nullptr, env, lane);  // ends on a barrier
 
     if (lane < NB) {
         const int b = lane;
-        const m3 R = ldm(sR[b]);
-        const float m = M.mass[b];
-        const v3 rc = mul(R, ld3(M.com[b]));
-        const v3 c = ld3(sP[b]) + rc;
-        // I_w = R I R^T
-        const float* ib = M.inertia[b];
-        const m3 I{ib[0], ib[3], ib[4], ib[3], ib[1], ib[5], ib[4], ib[5], ib[2]};
-        const m3 RI = mul(R, I);
-        const float wxx = RI.a00 * R.a00 + RI.a01 * R.a01 + RI.a02 * R.a02;
-        const float wyy = RI.a10 * R.a10 + RI.a11 * R.a11 + RI.a12 * R.a12;
-        const float wzz = RI.a20 * R.a20 + RI.a21 * R.a21 + RI.a22 * R.a22;
-        const float wxy = RI.a00 * R.a10 + RI.a01 * R.a11 + RI.a02 * R.a12;
-        const float wxz = RI.a00 * R.a20 + RI.a01 * R.a21 + RI.a02 * R.a22;
-        const float wyz = RI.a10 * R.a20 + RI.a11 * R.a21 + RI.a12 * R.a22;
-        const m3 Iw{wxx, wxy, wxz, wxy, wyy, wyz, wxz, wyz, wzz};
+        sAnc[b] = M.anc[b];  // read after the barriers below
+        const BodyWorld B = body_world(S, P.model, b);
+        const float m = B.m;
+        const v3 c = B.c;
         float* o = sBody[b];
         o[0] = m;
         st3(o + 1, c * m);
         // parallel axes: I_o = I_w + m (|c|^2 1 - c c^T)
-        o[4] = wxx + m * (c.y * c.y + c.z * c.z);
-        o[5] = wyy + m * (c.x * c.x + c.z * c.z);
-        o[6] = wzz + m * (c.x * c.x + c.y * c.y);
-        o[7] = wxy - m * c.x * c.y;
-        o[8] = wxz - m * c.x * c.z;
-        o[9] = wyz - m * c.y * c.z;
-        // Newton-Euler at qdd = 0: f = m (a_c - g), t_c = I_w wd + w x I_w w, about o: n = t_c + c x f
+        o[4] = B.wxx + m * (c.y * c.y + c.z * c.z);
+        o[5] = B.wyy + m * (c.x * c.x + c.z * c.z);
+        o[6] = B.wzz + m * (c.x * c.x + c.y * c.y);
+        o[7] = B.wxy - m * c.x * c.y;
+        o[8] = B.wxz - m * c.x * c.z;
+        o[9] = B.wyz - m * c.y * c.z;
+        // Newton-Euler at qdd = 0: f = m (a_c - g), t_c = I_w wd + w x I_w w, about o: n = t_c + c x f.
+        // Inline, not a shared function: called as one, a_c's sums move behind the gravity branch, this
+        // translation unit's SLP pairing follows, and c changes in its last bits.
+        const m3 Iw{B.wxx, B.wxy, B.wxz, B.wxy, B.wyy, B.wyz, B.wxz, B.wyz, B.wzz};
         const v3 w = ld3(sW[b]), wd = ld3(sWd[b]);
-        const v3 ac = ld3(sA[b]) + cross(wd, rc) + cross(w, cross(w, rc));
+        const v3 ac = ld3(sA[b]) + cross(wd, B.rc) + cross(w, cross(w, B.rc));
         const v3 g = (P.flags & HD_FLAG_NO_GRAVITY) ? v3{0.f, 0.f, 0.f} : ld3(M.gravity);
         const v3 f = (ac - g) * m;
-        const v3 n = mul(Iw, wd) + cross(w, mul(Iw, w)) + cross(c, f);
-        st3(o + 10, n);
+        st3(o + 10, mul(Iw, wd) + cross(w, mul(Iw, w)) + cross(c, f));
         st3(o + 13, f);
     }
     for (int c = lane; c < NG; c += kWave) {
@@ -257,8 +121,8 @@ __global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
             w = v3{c == 3 ? 1.f : 0.f, c == 4 ? 1.f : 0.f, c == 5 ? 1.f : 0.f};  // about o itself: v_o = 0
         } else {
             const int j = 1 + (c - 6) / 3, i = (c - 6) % 3;
-            w = v3{sR[j][i], sR[j][3 + i], sR[j][6 + i]};  // a = R_j e_i
-            v = cross(ld3(sP[j]), w);                      // a x (o - p_j)
+            w = v3{S.R[j][i], S.R[j][3 + i], S.R[j][6 + i]};  // a = R_j e_i
+            v = cross(ld3(S.P[j]), w);                      // a x (o - p_j)
         }
         st3(sSF[c], w);
         st3(sSF[c] + 3, v);
@@ -325,13 +189,13 @@ __global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
                 v3 a{i == 0 ? 1.f : 0.f, i == 1 ? 1.f : 0.f, i == 2 ? 1.f : 0.f};
                 v3 pj{0.f, 0.f, 0.f};
                 if (c >= 6) {
-                    a = v3{sR[j][i], sR[j][3 + i], sR[j][6 + i]};
-                    pj = ld3(sP[j]);
+                    a = v3{S.R[j][i], S.R[j][3 + i], S.R[j][6 + i]};
+                    pj = ld3(S.P[j]);
                 }
                 const v3 zero{0.f, 0.f, 0.f};
                 for (int b = 0; b < NB; ++b) {
                     const bool in = (sAnc[b] >> j & 1u) != 0;  // exact zeros outside j's subtree
-                    v3 l = lin ? a : cross(a, ld3(sP[b]) - pj);
+                    v3 l = lin ? a : cross(a, ld3(S.P[b]) - pj);
                     v3 w = lin ? zero : a;
                     if (!in) l = zero, w = zero;
                     float* row = out + b * kJacBody + c;
@@ -348,7 +212,7 @@ __global__ __launch_bounds__(kWave) void dynamics_kernel(const Params P) {
 struct hd_dynamics {
     int device = 0;
     int num_envs = 0;
-    DeviceArray<DModel> d_model;
+    DeviceArray<TreeModel> d_model;
 };
 
 extern "C" {
@@ -358,12 +222,7 @@ int hd_version(void) { return 1; }
 
 int hd_validate_model(const he_model* model) {
     if (check_model(model, "model", HE_MAX_BOXES)) return 1;
-    int depth[NB] = {0};  // this kernel's own bound: one pass per tree level
-    for (int b = 1; b < NB; ++b) {
-        depth[b] = depth[model->parents[b]] + 1;
-        if (depth[b] > kMaxDepth) return fail("model: body %d is %d joints from the root, at most %d", b, depth[b], kMaxDepth);
-    }
-    return 0;
+    return check_tree_depth(model);
 }
 
 int hd_create(int device, const he_model* model, const float gravity[3], int num_envs, hd_dynamics** out) {
@@ -372,22 +231,8 @@ int hd_create(int device, const he_model* model, const float gravity[3], int num
     if (num_envs < 1) return fail("hd_create: num_envs %d < 1", num_envs);
     if (!gravity) return fail("hd_create: null gravity vector");
     if (hd_validate_model(model)) return 1;
-    DModel dm{};
-    for (int b = 0; b < NB; ++b) {
-        const int a = model->parents[b];
-        dm.parent[b] = a;
-        dm.depth[b] = b == 0 ? 0 : dm.depth[a] + 1;
-        dm.anc[b] = (b == 0 ? 0u : dm.anc[a]) | 1u << b;
-        if (dm.depth[b] > dm.max_depth) dm.max_depth = dm.depth[b];
-        dm.mass[b] = model->mass[b];
-        for (int c = 0; c < 3; ++c) dm.local_pos[b][c] = model->local_pos[b][c], dm.com[b][c] = model->com[b][c];
-        for (int c = 0; c < 6; ++c) dm.inertia[b][c] = model->inertia[b][c];
-    }
-    for (int b = 0; b < NB; ++b)
-        for (int d = 0; d < NB; ++d)
-            if (dm.anc[d] >> b & 1u) dm.sub[b] |= 1u << d;
-    for (int d = 0; d < ND; ++d) dm.armature[d] = model->armature[d];
-    for (int c = 0; c < 3; ++c) dm.gravity[c] = gravity[c];
+    TreeModel dm;
+    fill_tree_model(model, gravity, dm);
     if (select_device(device, "hd_create")) return 1;
     std::unique_ptr<hd_dynamics> h(new hd_dynamics);  // a failed step below frees it and its array
     h->device = device;
@@ -410,10 +255,8 @@ int hd_compute(hd_dynamics* h, const float* root_state, const float* dof_state, 
     if (!root_state || !dof_state) return fail("hd_compute: null state pointer");
     if (!jac_out && !mass_out && !bias_out) return fail("hd_compute: no output buffer");
     if (flags & ~HD_FLAGS_ALL) return fail("hd_compute: unknown flag bits 0x%x", flags & ~HD_FLAGS_ALL);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(root_state) | reinterpret_cast<uintptr_t>(dof_state) |
-                         reinterpret_cast<uintptr_t>(jac_out) | reinterpret_cast<uintptr_t>(mass_out) |
-                         reinterpret_cast<uintptr_t>(bias_out);
-    if (al & 3u) return fail("hd_compute: every buffer must be 4-byte aligned");
+    if (misaligned({root_state, dof_state, jac_out, mass_out, bias_out}))
+        return fail("hd_compute: every buffer must be 4-byte aligned");
     Params P{};
     P.model = h->d_model;
     P.root = root_state;

@@ -1,17 +1,19 @@
-// he_host.h -- the host layer shared by the three C-ABI libraries (engine, renderer, dynamics): the
-// error text, the HIP call check, device selection, the structural he_model check and the owning
-// device array. Host code only, and nothing but the HIP runtime API and the standard library, so a
+// he_host.h -- the host layer shared by the four C-ABI libraries (engine, renderer, dynamics, solves):
+// the error text, the HIP call check, device selection, the buffer alignment check, the structural
+// he_model check and the owning device array. Host code only, and nothing but the HIP runtime API and the standard library, so a
 // plain C++ compiler builds it (tests/host/ does, against a counting allocator, under a sanitizer).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <cstdarg>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 
 // Everything here has internal linkage: each library keeps an error text of its own, also when all
-// three are loaded into one process. A library made of several translation units includes this
+// four are loaded into one process. A library made of several translation units includes this
 // header in one of them and hands the others a function (the engine: he_fail_text).
 namespace {
 
@@ -45,7 +47,14 @@ int select_device(int device, const char* who) {
     return 0;
 }
 
-// The structure every kernel of the three libraries is built for: the body and dof counts, the pair
+// the alignment every kernel assumes of a caller's buffers (plain dword accesses); null passes
+bool misaligned(std::initializer_list<const void*> ps) {
+    uintptr_t al = 0;
+    for (const void* p : ps) al |= reinterpret_cast<uintptr_t>(p);
+    return (al & 3u) != 0;
+}
+
+// The structure every kernel of the libraries is built for: the body and dof counts, the pair
 // table's bound, body 0 as the root, parents before children, the three geom types and at most
 // max_boxes boxes (the physics kernel's corner lanes). A template over include/humanoid_engine.h's
 // he_model, whose array lengths are the counts, so that this header needs no other.

@@ -1,9 +1,10 @@
 // libhumanoid_solve.so: the solves with the joint-space inertia M a controller calls each step
 // (include/humanoid_solve.h defines them). One launch, one 64-lane wave (= one block) per env, M never
 // leaves the wave:
-//   state      root row and the 69 (pos, vel) pairs into LDS; forward kinematics by tree level (the
-//              routine of hd_dynamics.hip restated, with the joints' accelerations carried when the entry
-//              has any), the bodies' inertias and Newton-Euler wrenches about their centres of mass,
+//   state      root row and the 69 (pos, vel) pairs into LDS; forward kinematics by tree level
+//              (he_tree_state.h, the routine hd_dynamics.hip runs too, with the joints' accelerations
+//              carried when the entry has any), the bodies' inertias and Newton-Euler wrenches about their
+//              centres of mass,
 //              their subtree sums about each joint's own origin, and per column the axis, the pivot and
 //              F = I^c S;
 //   solve_kernel (hs_forward_dynamics, hs_solve)
@@ -29,33 +30,15 @@
 #include "he_host.h"
 #include "he_regla.h"
 #include "he_topo.h"
+#include "he_tree_state.h"
 
 namespace {
 
-constexpr int NB = HE_NUM_BODIES;
-constexpr int ND = HE_NUM_DOF;
-constexpr int NG = HE_NUM_GEN;
-constexpr int kWave = 64;
 constexpr int NH = NG - kWave;  // the 11-column tail: second register set of lanes 0..10
-constexpr int kMaxDepth = 8;    // joints on the longest chain (he_topo.h body_chain)
 static_assert(NB == smpl::kNB && NG == smpl::kNG, "he_regla.h is unrolled for this tree");
 
-// what the kernels read of the model (hs_create)
-struct DModel {
-    int32_t parent[NB];
-    int32_t depth[NB];
-    uint32_t sub[NB];  // bit d: d in subtree(b)
-    float local_pos[NB][3];
-    float mass[NB];
-    float com[NB][3];
-    float inertia[NB][6];  // xx yy zz xy xz yz
-    float armature[ND];
-    float gravity[3];
-    int32_t max_depth;
-};
-
 struct Params {
-    const DModel* model;
+    const TreeModel* model;
     const float* root;       // [N,13]
     const float* dof;        // [N*69,2]
     const float* gen_force;  // [N,75] or null
@@ -67,80 +50,9 @@ struct Params {
     uint32_t flags;
 };
 
-struct v3 {
-    float x, y, z;
-};
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ v3 operator*(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-// S . F = w . n + v . p in one fixed order of fused multiply-adds
-__device__ __forceinline__ float dot6(v3 w, v3 v, v3 n, v3 p) {
-    return fmaf(v.z, p.z, fmaf(v.y, p.y, fmaf(v.x, p.x, fmaf(w.z, n.z, fmaf(w.y, n.y, w.x * n.x)))));
-}
-__device__ __forceinline__ v3 ld3(const float* p) { return v3{p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st3(float* p, v3 a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
-
-// a 3x3 matrix in named registers (row-major): no indexed register arrays
-struct m3 {
-    float a00, a01, a02, a10, a11, a12, a20, a21, a22;
-};
-__device__ __forceinline__ v3 mul(const m3& m, v3 v) {
-    return v3{m.a00 * v.x + m.a01 * v.y + m.a02 * v.z, m.a10 * v.x + m.a11 * v.y + m.a12 * v.z,
-              m.a20 * v.x + m.a21 * v.y + m.a22 * v.z};
-}
-__device__ __forceinline__ m3 mul(const m3& a, const m3& b) {
-    return m3{a.a00 * b.a00 + a.a01 * b.a10 + a.a02 * b.a20, a.a00 * b.a01 + a.a01 * b.a11 + a.a02 * b.a21,
-              a.a00 * b.a02 + a.a01 * b.a12 + a.a02 * b.a22, a.a10 * b.a00 + a.a11 * b.a10 + a.a12 * b.a20,
-              a.a10 * b.a01 + a.a11 * b.a11 + a.a12 * b.a21, a.a10 * b.a02 + a.a11 * b.a12 + a.a12 * b.a22,
-              a.a20 * b.a00 + a.a21 * b.a10 + a.a22 * b.a20, a.a20 * b.a01 + a.a21 * b.a11 + a.a22 * b.a21,
-              a.a20 * b.a02 + a.a21 * b.a12 + a.a22 * b.a22};
-}
-__device__ __forceinline__ m3 ldm(const float* p) { return m3{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]}; }
-__device__ __forceinline__ void stm(float* p, const m3& m) {
-    p[0] = m.a00, p[1] = m.a01, p[2] = m.a02, p[3] = m.a10, p[4] = m.a11, p[5] = m.a12, p[6] = m.a20, p[7] = m.a21,
-    p[8] = m.a22;
-}
-
-// exp([v]x) = 1 + A K + B K^2, A = sin(th) / th, B = 2 sin^2(th / 2) / th^2; below 1e-3 rad the series
-__device__ __forceinline__ m3 rodrigues(v3 v) {
-    const float t2 = dot(v, v);
-    float A, B;
-    if (t2 < 1e-6f) {
-        A = 1.f - t2 * (1.f / 6.f);
-        B = 0.5f - t2 * (1.f / 24.f);
-    } else {
-        const float th = sqrtf(t2);
-        const float sh = sinf(0.5f * th);
-        A = sinf(th) / th;
-        B = 2.f * sh * sh / t2;
-    }
-    const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z;
-    const float xy = B * v.x * v.y, xz = B * v.x * v.z, yz = B * v.y * v.z;
-    return m3{1.f - B * (yy + zz), xy - A * v.z, xz + A * v.y, xy + A * v.z, 1.f - B * (xx + zz), yz - A * v.x,
-              xz - A * v.y, yz + A * v.x, 1.f - B * (xx + yy)};
-}
-
-__device__ __forceinline__ m3 quat_matrix(float x, float y, float z, float w) {
-    const float n2 = x * x + y * y + z * z + w * w;
-    if (n2 < 1e-24f) return m3{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    const float s = 2.f / n2;
-    return m3{1.f - s * (y * y + z * z), s * (x * y - z * w), s * (x * z + y * w), s * (x * y + z * w),
-              1.f - s * (x * x + z * z), s * (y * z - x * w), s * (x * z - y * w), s * (y * z + x * w),
-              1.f - s * (x * x + y * y)};
-}
-
-__device__ __forceinline__ int col_joint(int c) { return c < 6 ? 0 : 1 + (c - 6) / 3; }
-
 // one env's working set (9.8 KB of LDS; solve_kernel adds the factor's 5.3 KB)
 struct Lds {
-    float q[ND], u[ND], qdd[ND];  // qdd: the joints' accelerations (torque_kernel), else unused
-    float R[NB][9];               // world rotation, row-major
-    float P[NB][3];               // origin relative to the root origin o
-    float W[NB][3];               // world angular velocity
-    float Wd[NB][3];              // world angular acceleration (root's: 0)
-    float A[NB][3];               // origin acceleration (root's: 0)
+    float q[ND], u[ND], qdd[ND], R[NB][9], P[NB][3], W[NB][3], Wd[NB][3], A[NB][3];  // what TreeState views
     float body[NB][16];           // m, centre of mass c3 (relative to o), I_w about it (xx yy zz xy xz yz), t_c3, f3
     float comp[NB][16];           // subtree j about its joint origin p_j: m, first moment h3, inertia 6, wrench (n3, f3)
     alignas(16) float SF[NG][12];  // per column: axis w, pivot (relative to o), then F = I^c S about the pivot (n, p)
@@ -153,53 +65,12 @@ struct Factor {
     int8_t dof_depth[NG];
 };
 
-// state -> S, F per column and the RNEA force per column. QDD: the joints' accelerations L.qdd enter the
-// bodies' accelerations (the root's stay 0: its columns are handled by the caller).
+// state -> S, F per column and the RNEA force per column. QDD: the joints' accelerations P.qdd_des enter
+// the bodies' accelerations (tree_kinematics).
 template <bool QDD>
-__device__ __forceinline__ void columns(Lds& L, const DModel& M, const Params& P, size_t env, int lane) {
-    for (int d = lane; d < ND; d += kWave) {
-        const float* row = P.dof + (env * ND + d) * 2;
-        L.q[d] = row[0];
-        L.u[d] = row[1];
-        if (QDD) L.qdd[d] = P.qdd_des[env * ND + d];
-    }
-    const float* root = P.root + env * 13;
-    m3 Rl{};  // body b >= 1: the joint's rotation; filled after the barrier below
-    int depth = -1, parent = 0;
-    if (lane < NB) {
-        depth = M.depth[lane];
-        parent = M.parent[lane];
-        if (lane == 0) {
-            stm(L.R[0], quat_matrix(root[3], root[4], root[5], root[6]));
-            st3(L.P[0], v3{0.f, 0.f, 0.f});
-            st3(L.W[0], ld3(root + 10));
-            st3(L.Wd[0], v3{0.f, 0.f, 0.f});
-            st3(L.A[0], v3{0.f, 0.f, 0.f});
-        }
-    }
-    __syncthreads();
-    if (lane >= 1 && lane < NB) Rl = rodrigues(ld3(&L.q[3 * (lane - 1)]));
-
-    // one pass per tree level (max_depth is the model's: the same in every lane)
-    const int levels = M.max_depth;
-    for (int lvl = 1; lvl <= levels; ++lvl) {
-        if (depth == lvl) {
-            const int b = lane, a = parent;
-            const m3 Ra = ldm(L.R[a]);
-            const v3 wa = ld3(L.W[a]), wda = ld3(L.Wd[a]);
-            const m3 Rb = mul(Ra, Rl);
-            const v3 d = mul(Ra, ld3(M.local_pos[b]));
-            const v3 wrel = mul(Rb, ld3(&L.u[3 * (b - 1)]));
-            v3 wd = wda + cross(wa, wrel);
-            if (QDD) wd = wd + mul(Rb, ld3(&L.qdd[3 * (b - 1)]));
-            stm(L.R[b], Rb);
-            st3(L.P[b], ld3(L.P[a]) + d);
-            st3(L.W[b], wa + wrel);
-            st3(L.Wd[b], wd);
-            st3(L.A[b], ld3(L.A[a]) + cross(wda, d) + cross(wa, cross(wa, d)));
-        }
-        __syncthreads();
-    }
+__device__ __forceinline__ void columns(Lds& L, const TreeModel& M, const Params& P, size_t env, int lane) {
+    const TreeState S{L.q, L.u, L.qdd, L.R, L.P, L.W, L.Wd, L.A};
+    tree_kinematics<QDD>(S, &M, P.root, P.dof, P.qdd_des, env, lane);  // ends on a barrier
 
     if (lane < NB) {
         const int b = lane;
@@ -344,7 +215,7 @@ __global__ __launch_bounds__(kWave, 2) void solve_kernel(const Params P) {
     __shared__ Factor Fc;
     const int lane = threadIdx.x;
     const size_t env = blockIdx.x;
-    const DModel& M = *P.model;
+    const TreeModel& M = *P.model;
     const bool hi = lane < NH;
 
     for (int i = lane; i < smpl::kNpack + 4; i += kWave) Fc.Lp[i] = 0.f;
@@ -402,7 +273,7 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
     __shared__ Lds L;
     const int lane = threadIdx.x;
     const size_t env = blockIdx.x;
-    const DModel& M = *P.model;
+    const TreeModel& M = *P.model;
     columns<true>(L, M, P, env, lane);  // L.bias = w, the RNEA force at qdd = (0; qdd_des); ends on a barrier
 
     // the base block of M: row i = (F_i's linear part, F_i's angular part) of root column i, the
@@ -468,16 +339,8 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
 struct hs_solver {
     int device = 0;
     int num_envs = 0;
-    DeviceArray<DModel> d_model;
+    DeviceArray<TreeModel> d_model;
 };
-
-namespace {
-bool misaligned(std::initializer_list<const void*> ps) {
-    uintptr_t al = 0;
-    for (const void* p : ps) al |= reinterpret_cast<uintptr_t>(p);
-    return (al & 3u) != 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -486,11 +349,7 @@ int hs_version(void) { return 1; }
 
 int hs_validate_model(const he_model* model) {
     if (check_model(model, "model", HE_MAX_BOXES)) return 1;
-    int depth[NB] = {0};  // one kinematics pass per tree level
-    for (int b = 1; b < NB; ++b) {
-        depth[b] = depth[model->parents[b]] + 1;
-        if (depth[b] > kMaxDepth) return fail("model: body %d is %d joints from the root, at most %d", b, depth[b], kMaxDepth);
-    }
+    if (check_tree_depth(model)) return 1;
     for (int b = 0; b < NB; ++b)  // the factorisation's register indices are this tree's
         if (model->parents[b] != smpl::kParentBody[b])
             return fail("model: body %d hangs on body %d; the factorisation is unrolled for a tree where it hangs on %d", b,
@@ -504,23 +363,8 @@ int hs_create(int device, const he_model* model, const float gravity[3], int num
     if (num_envs < 1) return fail("hs_create: num_envs %d < 1", num_envs);
     if (!gravity) return fail("hs_create: null gravity vector");
     if (hs_validate_model(model)) return 1;
-    DModel dm{};
-    uint32_t anc[NB] = {0};
-    for (int b = 0; b < NB; ++b) {
-        const int a = model->parents[b];
-        dm.parent[b] = a;
-        dm.depth[b] = b == 0 ? 0 : dm.depth[a] + 1;
-        anc[b] = (b == 0 ? 0u : anc[a]) | 1u << b;
-        if (dm.depth[b] > dm.max_depth) dm.max_depth = dm.depth[b];
-        dm.mass[b] = model->mass[b];
-        for (int c = 0; c < 3; ++c) dm.local_pos[b][c] = model->local_pos[b][c], dm.com[b][c] = model->com[b][c];
-        for (int c = 0; c < 6; ++c) dm.inertia[b][c] = model->inertia[b][c];
-    }
-    for (int b = 0; b < NB; ++b)
-        for (int d = 0; d < NB; ++d)
-            if (anc[d] >> b & 1u) dm.sub[b] |= 1u << d;
-    for (int d = 0; d < ND; ++d) dm.armature[d] = model->armature[d];
-    for (int c = 0; c < 3; ++c) dm.gravity[c] = gravity[c];
+    TreeModel dm;
+    fill_tree_model(model, gravity, dm);
     if (select_device(device, "hs_create")) return 1;
     std::unique_ptr<hs_solver> h(new hs_solver);  // a failed step below frees it and its array
     h->device = device;

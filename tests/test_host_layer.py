@@ -1,4 +1,4 @@
-"""CPU checks of the host layer the three C-ABI libraries share (humanoid_amd/csrc/he_host.h): the
+"""CPU checks of the host layer the four C-ABI libraries share (humanoid_amd/csrc/he_host.h): the
 owning device arrays under a host sanitizer, as a stand-alone program against a counting allocator
 (tests/host/device_array_test.cpp), and the error text, which each library keeps for itself."""
 import ctypes as C
@@ -47,11 +47,11 @@ def test_host_header_is_host_only():
 
 
 def test_each_library_keeps_its_own_error_text(he_model):
-    """All three libraries in one process: an argument error in each leaves the others' text alone."""
-    from humanoid_amd import build, dynamics, engine, render
-    if not all(os.path.exists(p) for p in (engine.LIB_PATH, render.LIB_PATH, dynamics.LIB_PATH)):
+    """All four libraries in one process: an argument error in each leaves the others' text alone."""
+    from humanoid_amd import build, dynamics, engine, render, solve
+    if not all(os.path.exists(p) for p in (engine.LIB_PATH, render.LIB_PATH, dynamics.LIB_PATH, solve.LIB_PATH)):
         build.build()
-    he, hr, hd = engine.load_library(), render.load_library(), dynamics.load_library()
+    he, hr, hd, hs = engine.load_library(), render.load_library(), dynamics.load_library(), solve.load_library()
     assert hd.hd_compute(None, None, None, None, None, None, 1, None) != 0
     assert hr.hr_render(None, None, None, None, None, 3, None) != 0
     assert he.he_create(None, 0, None) != 0
@@ -67,3 +67,8 @@ def test_each_library_keeps_its_own_error_text(he_model):
     m = C.c_void_p()
     assert hr.hr_create(0, None, 4, C.byref(m)) != 0 and hr.hr_last_error().decode() == "hr_create: null model"
     assert "he_gae" in he.he_last_error().decode()
+    # the fourth library: its refusal leaves the other three texts as they are
+    before = [f().decode() for f in (hd.hd_last_error, hr.hr_last_error, he.he_last_error)]
+    assert hs.hs_solve(None, None, None, None, None, 1, 1, None) != 0
+    assert hs.hs_last_error().decode() == "hs_solve: null handle"
+    assert [f().decode() for f in (hd.hd_last_error, hr.hr_last_error, he.he_last_error)] == before
