@@ -3,6 +3,7 @@ library ``humanoid_amd/libhumanoid_render.so``, the dynamics-query library
 ``humanoid_amd/libhumanoid_dynamics.so`` and the joint-space solve library
 ``humanoid_amd/libhumanoid_solve.so`` for gfx950 with hipcc (in-tree, they travel with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
+import glob
 import hashlib
 import os
 import re
@@ -49,11 +50,14 @@ SOURCES = [
     ("he_rollout.hip", ["-ffp-contract=off"]),  # GAE: the Cython module's float32 rounding
     ("he_engine.cpp", ["-x", "hip"]),
 ]
-HEADERS = ["he_host.h", "he_tree_state.h", "he_kernels.h", "he_math.h", "he_imitation_env.h", "he_topo.h", "he_regla.h", "he_smpl_topo.h", os.path.join("..", "..", "include", "humanoid_engine.h"),
-           os.path.join("..", "..", "include", "humanoid_rollout.h"),
-           os.path.join("..", "..", "include", "humanoid_render.h"),
-           os.path.join("..", "..", "include", "humanoid_dynamics.h"),
-           os.path.join("..", "..", "include", "humanoid_solve.h")]
+# every header under csrc/ and include/, relative to csrc/: a change to any of them rebuilds every object
+HEADERS = sorted(os.path.relpath(h, CSRC) for d in (CSRC, os.path.join(HERE, "..", "include"))
+                 for h in glob.glob(os.path.join(d, "*.h")))
+# (library, its sources, extra flags by source): a source with extra flags gets an object of its own
+# (<source>.phases.o), every other object is shared with the library that built it first
+LIBRARIES = [(LIB, SOURCES, {}), (PHASES_LIB, SOURCES, PHASES_DEFS), (RENDER_LIB, RENDER_SOURCES, {}),
+             (DYNAMICS_LIB, DYNAMICS_SOURCES, {}), (SOLVE_LIB, SOLVE_SOURCES, {})]
+COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
 def _hipcc():
@@ -61,6 +65,23 @@ def _hipcc():
         if c and (os.path.sep not in c or os.path.exists(c)):
             return c
     raise RuntimeError("hipcc not found")
+
+
+def compile_command(src, extra=(), device_only=False, out=None):
+    """The full hipcc argument list for one source, the one statement of how a kernel source is compiled
+    (build() and the tools under tools/ all take it from here): the common flags, the compilation-unit
+    id, the source's own flags (SOURCES and its like), then `extra`. src: a file name under csrc/, or a
+    path to a copy elsewhere (flags and id follow the file name). device_only: the gfx950 code object
+    alone, for the tools that hash or disassemble it. out: the object, by default _build/<name>.o."""
+    name = os.path.basename(src)
+    flags = {s: f for _, sources, _ in LIBRARIES for s, f in sources}[name]
+    # hipcc's default compilation-unit id hashes the source's absolute path into the device
+    # symbols of every anonymous-namespace kernel, so device_code_id() would follow the
+    # checkout directory; an id from the file name keeps it equal in every checkout
+    cuid = "-cuid=" + hashlib.md5(name.encode()).hexdigest()[:16]
+    device = ["--cuda-device-only", "--no-gpu-bundle-output"] if device_only else []
+    return [_hipcc()] + COMMON + [cuid] + flags + list(extra) + device + \
+        ["-c", src if os.path.dirname(src) else os.path.join(CSRC, src), "-o", out or os.path.join(BUILD, name + ".o")]
 
 
 def _mtime(p):
@@ -90,45 +111,51 @@ NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_ker
 MAX_SPILLS = {"he_physics.hip": {"physics_kernel_tgs": (148, 36), "physics_kernel": (0, 0)}}
 
 
+_REPORT_FIELDS = {"Occupancy [waves/SIMD]": "occupancy", "ScratchSize [bytes/lane]": "scratch",
+                  "VGPRs Spill": "spilled_vgprs"}
+
+
+def resource_report(stderr):
+    """The compiler's kernel-resource-usage remarks as {function name: block}. A block has "fields", every
+    line of the function's report as printed ({"VGPRs": "256", ...}), and as ints "occupancy" (waves per
+    SIMD), "scratch" (bytes per lane) and "spilled_vgprs", each None when the report lacks its line."""
+    report, block = {}, None
+    for ln in stderr.splitlines():
+        if "Function Name:" in ln:
+            block = report.setdefault(ln.split("Function Name:")[1].split()[0],
+                                      dict.fromkeys(_REPORT_FIELDS.values(), None) | {"fields": {}})
+            continue
+        m = re.search(r"remark:\s+([^:]+):\s+(\S+)", ln)
+        if m and block is not None:
+            key = m.group(1).strip()
+            block["fields"][key] = m.group(2)
+            if key in _REPORT_FIELDS and m.group(2).isdigit():
+                block[_REPORT_FIELDS[key]] = int(m.group(2))
+    return report
+
+
 def _check_scratch(src, stderr):
     names = NO_SCRATCH.get(os.path.basename(src))
     if not names:
         return
+    report = resource_report(stderr)
     for name in (names,) if isinstance(names, str) else names:
-        _check_kernel_scratch(name, stderr.splitlines())
-
-
-def _check_kernel_scratch(name, lines):
-    for i, ln in enumerate(lines):
-        if "Function Name:" in ln and name in ln:
-            for ln2 in lines[i + 1:]:
-                if "Function Name:" in ln2:
-                    break
-                m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln2)
-                if m:
-                    if int(m.group(1)) != 0:
-                        raise RuntimeError(f"{name}: {m.group(1)} bytes/lane of scratch (spills or a stack)")
-                    return
-    raise RuntimeError(f"{name}: no scratch size in the compiler's resource report")
+        scratch = [b["scratch"] for fn, b in report.items() if name in fn and b["scratch"] is not None]
+        if not scratch:
+            raise RuntimeError(f"{name}: no scratch size in the compiler's resource report")
+        if scratch[0] != 0:
+            raise RuntimeError(f"{name}: {scratch[0]} bytes/lane of scratch (spills or a stack)")
 
 
 def _check_spills(src, stderr):
     """Every kernel named in MAX_SPILLS must appear in the resource report, within its ceilings."""
+    report = resource_report(stderr)
     for name, (max_bytes, max_vgprs) in MAX_SPILLS.get(os.path.basename(src), {}).items():
-        lines = stderr.splitlines()
-        found = {}
-        for i, ln in enumerate(lines):
-            # the mangled name: <length><name>E<argument types>
-            if "Function Name:" in ln and re.search(r"\d" + name + r"E", ln):
-                for ln2 in lines[i + 1:]:
-                    if "Function Name:" in ln2:
-                        break
-                    m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", ln2)
-                    if m:
-                        found[m.group(1)] = int(m.group(2))
-        if len(found) != 2:
+        # the mangled name: <length><name>E<argument types>
+        got = [(b["scratch"], b["spilled_vgprs"]) for fn, b in report.items() if re.search(r"\d" + name + r"E", fn)]
+        if not got or None in got[-1]:
             raise RuntimeError(f"{name}: no scratch size / spill count in the compiler's resource report")
-        got = (found["ScratchSize [bytes/lane]"], found["VGPRs Spill"])
+        got = got[-1]
         if got[0] > max_bytes or got[1] > max_vgprs:
             raise RuntimeError(f"{name}: {got[0]} bytes/lane of scratch, {got[1]} spilled VGPRs; the ceiling is "
                                f"{max_bytes} / {max_vgprs} (list the kernel's scratch reloads: DESIGN §4.1)")
@@ -141,29 +168,16 @@ def _check_occupancy(src, stderr):
     if not want:
         return
     name, waves = want
-    lines = stderr.splitlines()
-    seen = 0
-    for i, ln in enumerate(lines):
-        if "Function Name:" in ln and name in ln:
-            fn = ln.split("Function Name:")[1].split()[0]
-            # every watched kernel must report its occupancy before the next function's report starts
-            occ = None
-            for ln2 in lines[i + 1:]:
-                if "Function Name:" in ln2:
-                    break
-                m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", ln2)
-                if m:
-                    occ = int(m.group(1))
-                    break
-            if occ is None:
-                raise RuntimeError(f"{fn}: no occupancy line in the compiler's resource report")
-            if occ < waves:
-                raise RuntimeError(f"{fn}: occupancy {occ} waves/SIMD < {waves} "
-                                   "(register pressure; see the resource report)")
-            seen += 1
-    if seen < MIN_KERNELS.get(os.path.basename(src), 1):
-        raise RuntimeError(f"{name}: {seen} kernel(s) in the compiler's resource report, "
-                           f"{MIN_KERNELS.get(os.path.basename(src), 1)} expected")
+    watched = {fn: b["occupancy"] for fn, b in resource_report(stderr).items() if name in fn}
+    for fn, occ in watched.items():
+        if occ is None:
+            raise RuntimeError(f"{fn}: no occupancy line in the compiler's resource report")
+        if occ < waves:
+            raise RuntimeError(f"{fn}: occupancy {occ} waves/SIMD < {waves} "
+                               "(register pressure; see the resource report)")
+    expected = MIN_KERNELS.get(os.path.basename(src), 1)
+    if len(watched) < expected:
+        raise RuntimeError(f"{name}: {len(watched)} kernel(s) in the compiler's resource report, {expected} expected")
 
 
 def _compile(hipcc, cmd, src, o, force, hdr_time, verbose, product=False):
@@ -213,30 +227,16 @@ def _link(hipcc, lib, objs, force):
 def build(force=False, verbose=False):
     os.makedirs(BUILD, exist_ok=True)
     hipcc = _hipcc()
-    common = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
     hdr_time = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
-    for lib, defs, suffix in ((LIB, {}, ".o"), (PHASES_LIB, PHASES_DEFS, ".phases.o")):
+    for lib, sources, defs in LIBRARIES:
         objs = []
-        for src, flags in SOURCES:
-            s = os.path.join(CSRC, src)
-            o = os.path.join(BUILD, src + (suffix if src in defs else ".o"))
+        for src, _ in sources:
+            o = os.path.join(BUILD, src + (".phases.o" if src in defs else ".o"))
             objs.append(o)
-            # hipcc's default compilation-unit id hashes the source's absolute path into the device
-            # symbols of every anonymous-namespace kernel, so device_code_id() would follow the
-            # checkout directory; an id from the file name keeps it equal in every checkout
-            cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
-            cmd = [hipcc] + common + [cuid] + flags + defs.get(src, []) + ["-c", s, "-o", o]
-            _compile(hipcc, cmd, s, o, force and lib == LIB or force and src in defs, hdr_time, verbose,
-                     product=src not in defs)
-        _link(hipcc, lib, objs, force)
-    for lib, sources in ((RENDER_LIB, RENDER_SOURCES), (DYNAMICS_LIB, DYNAMICS_SOURCES), (SOLVE_LIB, SOLVE_SOURCES)):
-        objs = []
-        for src, flags in sources:
-            s = os.path.join(CSRC, src)
-            o = os.path.join(BUILD, src + ".o")
-            objs.append(o)
-            cuid = "-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]
-            _compile(hipcc, [hipcc] + common + [cuid] + flags + ["-c", s, "-o", o], s, o, force, hdr_time, verbose)
+            # an object shared with an earlier library was forced there; the ceilings on the register
+            # spills hold for the product objects only
+            _compile(hipcc, compile_command(src, defs.get(src, ()), out=o), os.path.join(CSRC, src), o,
+                     force and (not defs or src in defs), hdr_time, verbose, product=src not in defs)
         _link(hipcc, lib, objs, force)
     return LIB
 

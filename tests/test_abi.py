@@ -137,3 +137,112 @@ def test_occupancy_guard_removes_the_rejected_object(tmp_path, monkeypatch):
     remark = full.split("remark: Function Name: physics_kernel_tgs")[0]
     with pytest.raises(RuntimeError, match="2 expected"):
         build._compile("hipcc", cmd, str(src), o, True, 0.0, False)
+
+
+def _spill_report(**kernels):
+    """A resource report in the compiler's words: kernel name -> (scratch bytes per lane, spilled VGPRs)."""
+    return "".join(f"remark: Function Name: _ZN12_GLOBAL__N_1{len(k)}{k}E8PhysArgs\nremark:     VGPRs: 256\n"
+                   f"remark:     ScratchSize [bytes/lane]: {b}\nremark:     Occupancy [waves/SIMD]: 2\n"
+                   f"remark:     SGPRs Spill: 65\nremark:     VGPRs Spill: {v}\n" for k, (b, v) in kernels.items())
+
+
+def test_spill_ceilings_read_the_named_kernel():
+    """build._check_spills holds each kernel of MAX_SPILLS to its own ceilings, by exact mangled name:
+    physics_kernel never reads physics_kernel_tgs's block, and a kernel missing from the report fails."""
+    from humanoid_amd import build
+    ceil_b, ceil_v = build.MAX_SPILLS["he_physics.hip"]["physics_kernel_tgs"]
+    assert build.MAX_SPILLS["he_physics.hip"]["physics_kernel"] == (0, 0) and ceil_b > 0 and ceil_v > 0
+    # both orders of the two blocks: the PGS kernel at 0 / 0, the TGS kernel at its ceiling
+    build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v)))
+    build._check_spills("he_physics.hip", _spill_report(physics_kernel_tgs=(ceil_b, ceil_v), physics_kernel=(0, 0)))
+    with pytest.raises(RuntimeError, match=rf"physics_kernel_tgs: {ceil_b + 1} bytes/lane of scratch, {ceil_v} spilled"):
+        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b + 1, ceil_v)))
+    with pytest.raises(RuntimeError, match=rf"physics_kernel_tgs: {ceil_b} bytes/lane of scratch, {ceil_v + 1} spilled"):
+        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v + 1)))
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: no scratch size / spill count"):
+        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0)))
+    with pytest.raises(RuntimeError, match="physics_kernel: no scratch size / spill count"):
+        build._check_spills("he_physics.hip", _spill_report(physics_kernel_tgs=(ceil_b, ceil_v)))
+    # a block without its spill line is a missing line, not a pass
+    cut = _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v)).replace(
+        f"remark:     VGPRs Spill: {ceil_v}\n", "")
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: no scratch size / spill count"):
+        build._check_spills("he_physics.hip", cut)
+    # only the TGS kernel exceeds: the error names it, in either order of the blocks, and never the PGS kernel
+    for order in (("physics_kernel", "physics_kernel_tgs"), ("physics_kernel_tgs", "physics_kernel")):
+        figures = {"physics_kernel": (0, 0), "physics_kernel_tgs": (ceil_b + 8, ceil_v + 2)}
+        with pytest.raises(RuntimeError) as e:
+            build._check_spills("he_physics.hip", _spill_report(**{k: figures[k] for k in order}))
+        assert str(e.value).startswith(f"physics_kernel_tgs: {ceil_b + 8} bytes/lane of scratch, {ceil_v + 2} spilled VGPRs")
+        assert f"{ceil_b} / {ceil_v}" in str(e.value)
+    # sources without ceilings are not checked
+    build._check_spills("hs_solve.hip", "")
+
+
+def test_compile_command_is_the_builds():
+    """build.compile_command gives, for every object of the five libraries, the line build() has always
+    written into the object's .cmd stamp (so a tree built before recompiles nothing for the flags' sake),
+    and tools/build_variant.py's line for the physics TU is the product's but for the object."""
+    import hashlib
+    import sys
+    from humanoid_amd import build
+    common = ["--offload-arch=" + build.ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
+    libraries = [(build.SOURCES, {}), (build.SOURCES, build.PHASES_DEFS), (build.RENDER_SOURCES, {}),
+                 (build.DYNAMICS_SOURCES, {}), (build.SOLVE_SOURCES, {})]
+    assert [s for _, s, _ in build.LIBRARIES] == [s for s, _ in libraries]
+    assert [d for _, _, d in build.LIBRARIES] == [d for _, d in libraries]
+    n = 0
+    for sources, defs in libraries:
+        for src, flags in sources:
+            o = os.path.join(build.BUILD, src + (".phases.o" if src in defs else ".o"))
+            want = [build._hipcc()] + common + ["-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]] + flags + \
+                defs.get(src, []) + ["-c", os.path.join(build.CSRC, src), "-o", o]
+            assert " ".join(build.compile_command(src, defs.get(src, ()), out=o)) == " ".join(want)
+            n += 1
+    assert n == 17
+    # the physics TU's line spelled out, and the default object
+    phys = os.path.join(build.CSRC, "he_physics.hip")
+    assert " ".join(build.compile_command("he_physics.hip")) == (
+        f"{build._hipcc()} --offload-arch={build.ARCH} -O3 -fPIC -std=c++17 -Wall -Wno-unused-function "
+        "-cuid=a5c8526841ebfadf -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize -mllvm "
+        f"-amdgpu-sched-strategy=max-ilp -c {phys} -o {os.path.join(build.BUILD, 'he_physics.hip.o')}")
+    # the tools' code object: the same line with the device-only pair in front of -c; a copy of the source
+    # elsewhere keeps the flags and the id of its file name
+    dev = build.compile_command("/elsewhere/he_physics.hip", ["-DX=1"], device_only=True, out="k.co")
+    assert dev[-7:] == ["-DX=1", "--cuda-device-only", "--no-gpu-bundle-output", "-c", "/elsewhere/he_physics.hip", "-o", "k.co"]
+    assert dev[:-7] == build.compile_command("he_physics.hip")[:-4]
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import build_variant
+    finally:
+        sys.path.pop(0)
+    cmd, obj = build_variant.variant_command("same", "he_physics.hip", [])
+    product = build.compile_command("he_physics.hip")
+    assert cmd[:-1] == product[:-1] and cmd[-1] == obj != product[-1]
+    # a variant's sched-strategy replaces the product's
+    cmd, _ = build_variant.variant_command("s", "he_physics.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"])
+    assert [c for c in cmd if c.startswith("-amdgpu-sched-strategy=")] == ["-amdgpu-sched-strategy=iterative-ilp"]
+    assert cmd.count("-mllvm") == product.count("-mllvm")
+
+
+def test_physics_headers_stand_alone(tmp_path):
+    """Each he_phys_*.h includes what it uses: a source that includes that header alone passes the
+    compiler's front end with the physics TU's own compile line."""
+    import glob
+    import shutil
+    from humanoid_amd import build
+    if shutil.which(build._hipcc()) is None:
+        pytest.skip("hipcc not present")
+    headers = sorted(glob.glob(os.path.join(build.CSRC, "he_phys_*.h")))
+    assert len(headers) >= 8
+    runs = []
+    for h in headers:  # the front ends side by side
+        d = tmp_path / os.path.basename(h)
+        d.mkdir()
+        src = d / "he_physics.hip"  # the flags follow the file name
+        src.write_text(f'#include "{h}"\n')
+        cmd = build.compile_command(str(src), ["-fsyntax-only"], device_only=True, out=str(d / "none.o"))
+        runs.append((h, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    for h, p in runs:
+        _, err = p.communicate()
+        assert p.returncode == 0, f"{os.path.basename(h)} does not compile on its own:\n{err}"

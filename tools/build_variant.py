@@ -11,22 +11,29 @@ sys.path.insert(0, ROOT)
 from humanoid_amd import build as B  # noqa: E402
 
 
+OUT_DIR = os.path.join(ROOT, "humanoid_amd", "_variants")
+
+
+def variant_command(name, tu, defs):
+    """The variant object's compile line (the product's, humanoid_amd.build.compile_command, with defs) and its path."""
+    obj = os.path.join(OUT_DIR, name + "." + tu + ".o")
+    cmd = B.compile_command(tu, defs, out=obj)
+    if any(d.startswith("-amdgpu-sched-strategy=") for d in defs) and "-amdgpu-sched-strategy=max-ilp" in dict(B.SOURCES)[tu]:
+        i = cmd.index("-amdgpu-sched-strategy=max-ilp")  # a variant's strategy replaces the product's (the first)
+        del cmd[i - 1:i + 1]
+    return cmd, obj
+
+
 def main():
     name, defs = sys.argv[1], sys.argv[2:]
     tu = "he_physics.hip"
     if defs[:1] == ["--tu"]:
         tu, defs = defs[1], defs[2:]
     B.build()
-    out_dir = os.path.join(ROOT, "humanoid_amd", "_variants")
+    out_dir = OUT_DIR
     os.makedirs(out_dir, exist_ok=True)
     hipcc = B._hipcc()
-    flags = list(dict(B.SOURCES)[tu])
-    if any(d.startswith("-amdgpu-sched-strategy=") for d in defs) and "-amdgpu-sched-strategy=max-ilp" in flags:
-        i = flags.index("-amdgpu-sched-strategy=max-ilp")  # a variant's strategy replaces the product's
-        del flags[i - 1:i + 1]
-    obj = os.path.join(out_dir, name + "." + tu + ".o")
-    cmd = [hipcc, "--offload-arch=" + B.ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"] + flags + defs + \
-          ["-c", os.path.join(B.CSRC, tu), "-o", obj]
+    cmd, obj = variant_command(name, tu, defs)
     subprocess.run(cmd, check=True)
     objs = [obj if src == tu else os.path.join(B.BUILD, src + ".o") for src, _ in B.SOURCES]
     lib = os.path.join(out_dir, name + ".so")

@@ -19,12 +19,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def code_hash(src, defs):
-    flags = dict(B.SOURCES)["he_physics.hip"]
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "k.co")
-        cmd = [B._hipcc(), "--offload-arch=" + B.ARCH, "-O3", "-fPIC", "-std=c++17", "--cuda-device-only", "--no-gpu-bundle-output",
-               "-c", src, "-o", co] + flags + defs
-        subprocess.run(cmd, check=True, capture_output=True)
+        subprocess.run(B.compile_command(src, defs, device_only=True, out=co), check=True, capture_output=True)
         h = hashlib.sha256()
         for sec in (".text", ".rodata"):
             out = os.path.join(td, sec[1:])

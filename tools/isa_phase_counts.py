@@ -51,12 +51,9 @@ def cls(op):
 
 
 def main():
-    src = os.path.join(B.CSRC, "he_physics.hip")
-    flags = dict(B.SOURCES)["he_physics.hip"]
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "k.co")
-        subprocess.run([B._hipcc(), "--offload-arch=" + B.ARCH, "-O3", "-fPIC", "-std=c++17", "--cuda-device-only",
-                        "--no-gpu-bundle-output", "-c", src, "-o", co] + flags + B.PHASES_DEFS["he_physics.hip"],
+        subprocess.run(B.compile_command("he_physics.hip", B.PHASES_DEFS["he_physics.hip"], device_only=True, out=co),
                        check=True, capture_output=True)
         dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
                              capture_output=True, text=True).stdout

@@ -25,26 +25,15 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 def main():
     w = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     kname = sys.argv[2] if len(sys.argv) > 2 else "physics_kernel"
-    src = os.path.join(B.CSRC, "he_physics.hip")
-    flags = dict(B.SOURCES)["he_physics.hip"]
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "k.co")
-        r = subprocess.run([B._hipcc(), "--offload-arch=" + B.ARCH, "-O3", "-fPIC", "-std=c++17", "--cuda-device-only",
-                            "--no-gpu-bundle-output", "-c", src, "-o", co, f"-DHE_MIN_WAVES={w}",
-                            "-Rpass-analysis=kernel-resource-usage"] + flags + B.PHASES_DEFS["he_physics.hip"],
+        extra = B.PHASES_DEFS["he_physics.hip"] + [f"-DHE_MIN_WAVES={w}", "-Rpass-analysis=kernel-resource-usage"]
+        r = subprocess.run(B.compile_command("he_physics.hip", extra, device_only=True, out=co),
                            check=True, capture_output=True, text=True)
         dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
                              capture_output=True, text=True).stdout
-    report = {}
-    lines = r.stderr.splitlines()
-    for i, ln in enumerate(lines):
-        if "Function Name:" in ln and re.search(r"\d" + kname + r"E", ln):
-            for ln2 in lines[i + 1:i + 14]:
-                if "Function Name:" in ln2:
-                    break
-                m = re.search(r"remark:\s+([^:]+):\s+(\S+)", ln2)
-                if m:
-                    report[m.group(1).strip()] = m.group(2)
+    # the kernel's block of the resource report, by its mangled name: <length><name>E<argument types>
+    report = next((b["fields"] for fn, b in B.resource_report(r.stderr).items() if re.search(r"\d" + kname + r"E", fn)), {})
     L = dis.split("\n")
     # the kernel's own disassembly: from its label to the next function label
     start = next(i for i, ln in enumerate(L) if re.search(r"\d" + kname + r"E\w*>:", ln))
