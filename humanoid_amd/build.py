@@ -1,7 +1,8 @@
 """Build ``humanoid_amd/libhumanoid_engine.so`` (with its diagnostic twin), the camera-sensor
 library ``humanoid_amd/libhumanoid_render.so``, the dynamics-query library
-``humanoid_amd/libhumanoid_dynamics.so`` and the joint-space solve library
-``humanoid_amd/libhumanoid_solve.so`` for gfx950 with hipcc (in-tree, they travel with the
+``humanoid_amd/libhumanoid_dynamics.so``, the joint-space solve library
+``humanoid_amd/libhumanoid_solve.so`` and the task-space control library
+``humanoid_amd/libhumanoid_task.so`` for gfx950 with hipcc (in-tree, they travel with the
 repo to the GPU box). Usage: ``python -m humanoid_amd.build [--force]``."""
 import glob
 import hashlib
@@ -31,6 +32,11 @@ DYNAMICS_SOURCES = [("hd_dynamics.hip", [])]
 SOLVE_LIB = os.path.join(HERE, "libhumanoid_solve.so")
 # no SLP vectorisation, as for the physics kernel: the elimination issues its packed FMAs itself
 SOLVE_SOURCES = [("hs_solve.hip", ["-fno-slp-vectorize"])]
+# task-space control (include/humanoid_task.h: the task Jacobian rows, J M^-1, the operational-space
+# inertia and the task solve in one launch): a fifth product library, which shares the solve kernels'
+# path from the state to the factor of M (he_joint_space.h) without being linked to their library
+TASK_LIB = os.path.join(HERE, "libhumanoid_task.so")
+TASK_SOURCES = [("ht_task.hip", ["-fno-slp-vectorize"])]
 BUILD = os.path.join(HERE, "_build")
 ARCH = os.environ.get("HE_OFFLOAD_ARCH", "gfx950")
 
@@ -57,6 +63,9 @@ HEADERS = sorted(os.path.relpath(h, CSRC) for d in (CSRC, os.path.join(HERE, "..
 # (<source>.phases.o), every other object is shared with the library that built it first
 LIBRARIES = [(LIB, SOURCES, {}), (PHASES_LIB, SOURCES, PHASES_DEFS), (RENDER_LIB, RENDER_SOURCES, {}),
              (DYNAMICS_LIB, DYNAMICS_SOURCES, {}), (SOLVE_LIB, SOLVE_SOURCES, {})]
+# libraries added since the list above was pinned by the tests of the first five: built after them, by the
+# same rules (compile_command looks their sources' flags up too)
+EXTENSION_LIBRARIES = [(TASK_LIB, TASK_SOURCES, {})]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -74,7 +83,7 @@ def compile_command(src, extra=(), device_only=False, out=None):
     path to a copy elsewhere (flags and id follow the file name). device_only: the gfx950 code object
     alone, for the tools that hash or disassemble it. out: the object, by default _build/<name>.o."""
     name = os.path.basename(src)
-    flags = {s: f for _, sources, _ in LIBRARIES for s, f in sources}[name]
+    flags = {s: f for _, sources, _ in LIBRARIES + EXTENSION_LIBRARIES for s, f in sources}[name]
     # hipcc's default compilation-unit id hashes the source's absolute path into the device
     # symbols of every anonymous-namespace kernel, so device_code_id() would follow the
     # checkout directory; an id from the file name keeps it equal in every checkout
@@ -89,8 +98,9 @@ def _mtime(p):
 
 
 # kernels whose occupancy (waves per SIMD, the compiler's resource report) the build enforces: the
-# physics kernel is one wave per env and latency-bound, and at one wave per SIMD it runs ~40 % slower
-MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2)}
+# physics kernel is one wave per env and latency-bound, and at one wave per SIMD it runs ~40 % slower;
+# the task kernel is solve_kernel's shape and declares the same two waves
+MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2), "ht_task.hip": ("task_kernel", 2)}
 # how many kernels of the TU match the watched name (physics_kernel and physics_kernel_tgs): a report
 # that lists fewer fails the build, so neither can drop out of the check unnoticed
 MIN_KERNELS = {"he_physics.hip": 2}
@@ -99,7 +109,7 @@ MIN_KERNELS = {"he_physics.hip": 2}
 # named registers and indexes only LDS; the solve kernels (a source names one kernel or a tuple of
 # them) hold the mass matrix and its factorisation in registers, within the 256 of two waves per SIMD
 NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_kernel",
-              "hs_solve.hip": ("solve_kernel", "torque_kernel")}
+              "hs_solve.hip": ("solve_kernel", "torque_kernel"), "ht_task.hip": "task_kernel"}
 # ceilings on the physics kernels' register spills, by exact kernel name: (scratch bytes per lane,
 # spilled VGPRs) of the compiler's resource report, no slack (as the occupancy). The TGS kernel's
 # spills are a plan, not a by-product: what is parked is the <= 32-row class's columns
@@ -228,7 +238,7 @@ def build(force=False, verbose=False):
     os.makedirs(BUILD, exist_ok=True)
     hipcc = _hipcc()
     hdr_time = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
-    for lib, sources, defs in LIBRARIES:
+    for lib, sources, defs in LIBRARIES + EXTENSION_LIBRARIES:
         objs = []
         for src, _ in sources:
             o = os.path.join(BUILD, src + (".phases.o" if src in defs else ".o"))

@@ -101,6 +101,7 @@ class Dynamics:
         self.mass_matrix = torch.zeros(shapes["mass_matrix"], dtype=torch.float32, device=self.device)
         self.bias = torch.zeros(shapes["bias"], dtype=torch.float32, device=self.device)
         self._solver = None  # humanoid_amd.solve.Solver, created by the first solve
+        self._task = None  # humanoid_amd.task.TaskSpace, created by the first use
 
     def __del__(self):
         _abi.destroy_handle(self, "hd_destroy")
@@ -160,6 +161,16 @@ class Dynamics:
             self._solver = Solver(self.engine, armature=self.armature)
         self._solver.armature, self._solver.gravity = self.armature, self.gravity
         return self._solver
+
+    @property
+    def task(self):
+        """The :class:`humanoid_amd.task.TaskSpace` of this engine (created on first use; its rows stay
+        set), with this object's ``armature`` and ``gravity`` settings."""
+        if getattr(self, "_task", None) is None:
+            from .task import TaskSpace
+            self._task = TaskSpace(self.engine, armature=self.armature)
+        self._task.armature, self._task.gravity = self.armature, self.gravity
+        return self._task
 
     def forward_dynamics(self, gen_force=None, out=None):
         """qdd [N,75] = M^-1 (gen_force - c) at the engine's current state: one launch, M never written."""

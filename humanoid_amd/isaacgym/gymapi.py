@@ -42,7 +42,11 @@ Engine-specific behaviour (documented, not silent):
 * ENGINE EXTENSION: the solves with that ``M``, each one HIP launch from the current state with ``M``
   kept in registers (``include/humanoid_solve.h``): ``solve_forward_dynamics`` (``qdd = M^-1 (f - c)``),
   ``solve_computed_torque`` (joint torques and base acceleration for desired joint accelerations) and
-  ``solve_mass_matrix`` (``M^-1`` on up to 32 rows per env, e.g. a Jacobian block).
+  ``solve_mass_matrix`` (``M^-1`` on up to 32 rows per env, e.g. a Jacobian block);
+* ENGINE EXTENSION: task-space control in one launch (``include/humanoid_task.h``): ``set_task_rows``
+  names up to 32 task rows (velocity components of points on bodies, the same for every env), and
+  ``solve_task_space`` gives the generalised force (``mode="force"``: ``J^T F``) or the joint torques
+  (``mode="joint"``, for ``set_dof_actuation_force_tensor``) that give those rows a desired acceleration.
 """
 from __future__ import annotations
 
@@ -235,6 +239,7 @@ class Sim:
         self.rendered = False
         self.dynamics = None          # humanoid_amd.dynamics.Dynamics, created by the first acquire
         self.dynamics_acquired = set()  # of "jacobian", "mass_matrix", "bias"
+        self.task_stage = None        # [N,75] the (0_6; tau) solve_task_space's joint mode writes
 
 
 # ----------------------------------------------------------------------------------- the Gym object
@@ -511,6 +516,46 @@ class Gym:
         """Engine extension: out [N,k,75] = M^-1 on each of the k <= 32 rows of rhs [N,k,75]."""
         dyn = self._solve_dynamics(sim, "solve_mass_matrix")
         dyn.solve(self._tensor(rhs_desc), self._tensor(out_desc))
+        return True
+
+    # -- task-space control (engine extensions) -----------------------------------------------------
+    def set_task_rows(self, sim: Sim, rows):
+        """Engine extension: the task rows of ``solve_task_space``, ``(body index or name, axis, point=(0, 0,
+        0))`` each: axis 0..2 is the world linear velocity component x / y / z of the point given in the body's
+        frame, 3..5 the body's world angular velocity component. 1 to 32 rows, the same for every env; they
+        replace the rows set before."""
+        dyn = self._solve_dynamics(sim, "set_task_rows")
+        dyn.task.set_rows(rows)
+        return True
+
+    def solve_task_space(self, sim: Sim, xdd_des_desc, tau_or_force_out_desc, mode="joint", damping=0.0,
+                         gen_force_desc=None, qdd_out_desc=None):
+        """Engine extension: what gives the task rows the accelerations xdd_des [N,k] at the current state.
+        ``mode="joint"``: the joint torques tau [N,69] of minimum norm (base unactuated), as
+        ``set_dof_actuation_force_tensor`` takes them; ``mode="force"``: the operational-space generalised
+        force J^T F [N,75]. ``gen_force_desc`` [N,75] is a generalised force already acting (a posture
+        torque there is projected into the task's null space); ``qdd_out_desc`` [N,75] takes the resulting
+        acceleration. The torques are not clamped to the effort limits."""
+        import torch
+        from ..task import MODES, TaskError
+        dyn = self._solve_dynamics(sim, "solve_task_space")
+        if mode not in MODES:
+            raise TaskError(f"solve_task_space: unknown mode {mode!r} (one of {sorted(MODES)})")
+        out = self._tensor(tau_or_force_out_desc)
+        joint = mode == "joint"
+        n = sim.engine.num_envs
+        if joint:  # the kernel writes (0_6; tau): through a [N,75] staging tensor into the caller's [N,69]
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, _abi.ND):
+                raise TaskError(f"tau_out: expected a tensor of shape ({n}, {_abi.ND}) in joint mode")
+            if sim.task_stage is None:
+                sim.task_stage = torch.empty(n, _abi.NG, dtype=torch.float32, device=sim.engine.device)
+        u, _, _ = dyn.task.control(self._tensor(xdd_des_desc),
+                                   None if gen_force_desc is None else self._tensor(gen_force_desc), mode, damping,
+                                   out=sim.task_stage if joint else out, want_task_force=False,
+                                   qdd=None if qdd_out_desc is None else self._tensor(qdd_out_desc),
+                                   want_qdd=qdd_out_desc is not None)
+        if joint:
+            out.copy_(u[:, 6:])
         return True
 
     def _flush(self, sim: Sim):

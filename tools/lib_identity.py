@@ -12,7 +12,9 @@ the per-env properties, `--scheme pgs` physics_kernel. --lying: 512 lying bodies
 plane (25-40 contacts, most solves past 32 rows: the TGS wide class) under random targets, 10 policy
 steps; with --max-contacts below the contacts generated it reaches the overflow reduction, and the
 count of envs that dropped contacts is printed (0: the mode did not reach it, lower the cap).
---queries: the two query libraries (libhumanoid_dynamics.so, libhumanoid_solve.so) of each directory on
+--queries: the query libraries (libhumanoid_dynamics.so, libhumanoid_solve.so, and libhumanoid_task.so when
+both directories hold one: its terms under the four flag combinations and both control modes at k = 1, 6,
+32) of each directory on
 the same engine library and 305 seeded states that reach the branches of csrc/he_tree_state.h (the five
 of tests/test_gpu_dynamics.py, roots at the origin and 1 km away, all dofs zero, a joint below, at and
 above rodrigues' 1e-3 rad threshold, a joint near pi): J, M, c under the four flag combinations,
@@ -75,7 +77,7 @@ np.savez(sys.argv[1], root=eng.root_states.cpu().numpy(), dof=eng.dof_state.cpu(
 """
 
 
-# argv: out, libhumanoid_dynamics.so, libhumanoid_solve.so
+# argv: out, libhumanoid_dynamics.so, libhumanoid_solve.so[, libhumanoid_task.so]
 CODE_QUERIES = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
@@ -83,6 +85,9 @@ import cases
 from humanoid_amd import dynamics, solve
 dynamics.load_library(sys.argv[2])  # before any constructor: the first load is the one that stays
 solve.load_library(sys.argv[3])
+if len(sys.argv) > 4:
+    from humanoid_amd import task
+    task.load_library(sys.argv[4])
 from humanoid_amd.engine import Engine
 from humanoid_amd.model import load_default_model
 G = 50  # envs per group
@@ -127,6 +132,23 @@ tau, a_b = sol.computed_torque(cu(rng.uniform(-20, 20, (n, 69))), cu(f))
 out['ct_tau'], out['ct_base_acc'] = tau.cpu().numpy(), a_b.cpu().numpy()
 for k in (1, 6, 32):
     out[f'solve_k{k}'] = sol.solve(cu(rng.normal(size=(n, k, 75)))).cpu().numpy()
+if len(sys.argv) > 4:  # the task library: every term and both modes at k = 1, 6 (offset points), 32
+    import task_reference as TR
+    from humanoid_amd.body_sets import BODY_NAMES
+    sets = TR.row_sets(list(BODY_NAMES))
+    off = (0.03, -0.02, 0.01)
+    sets[6] = [(b, a, off) for b, a, _ in sets[6]]
+    ts = task.TaskSpace(eng)
+    for k in (1, 6, 32):
+        ts.set_rows(sets[k])
+        xdd = cu(rng.uniform(-5, 5, (n, k)))
+        for flags in range(4):
+            out.update({f'task_{name}_k{k}_flags{flags}': v.cpu().numpy() for name, v in ts.terms(cu(f), flags=flags).items()})
+        for mode in ('force', 'joint'):
+            for lam in (0.0, 0.01):
+                names = (f'task_{x}_k{k}_{mode}_damping{lam}' for x in ('u', 'F', 'qdd'))
+                out.update({name: v.cpu().numpy() for name, v in zip(names, ts.control(xdd, cu(f), mode, lam))})
+    del ts
 torch.cuda.synchronize()
 np.savez(sys.argv[1], **out)
 del dyn, sol, eng  # before the interpreter takes the modules their destructors use
@@ -135,7 +157,8 @@ del dyn, sol, eng  # before the interpreter takes the modules their destructors 
 
 def queries(dirs):
     """--queries: the dynamics and solve libraries of two directories on the same seeded states (the same
-    product engine library on both sides), every output compared byte for byte."""
+    product engine library on both sides), every output compared byte for byte; the task library's outputs
+    too when both directories hold one."""
     import tempfile
     import numpy as np
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -144,10 +167,15 @@ def queries(dirs):
     differs = False
     with tempfile.TemporaryDirectory() as tmp:  # 70 MB a side: not among the records
         outs = []
+        with_task = all(os.path.exists(os.path.join(d, "libhumanoid_task.so")) for d in dirs)
+        if not with_task:
+            print("no libhumanoid_task.so on both sides: the task library's outputs are left out", flush=True)
         for k, d in enumerate(dirs):
-            libs = [os.path.abspath(os.path.join(d, name)) for name in ("libhumanoid_dynamics.so", "libhumanoid_solve.so")]
+            names = ("libhumanoid_dynamics.so", "libhumanoid_solve.so") + (("libhumanoid_task.so",) if with_task else ())
+            libs = [os.path.abspath(os.path.join(d, name)) for name in names]
             print(f"side {'AB'[k]}: {d}  device code: dynamics {build.device_code_id(libs[0])}, "
-                  f"solve {build.device_code_id(libs[1])}", flush=True)
+                  f"solve {build.device_code_id(libs[1])}" + (f", task {build.device_code_id(libs[2])}" if with_task else ""),
+                  flush=True)
             outs.append(os.path.join(tmp, f"queries_{k}.npz"))
             subprocess.run([sys.executable, "-c", CODE_QUERIES, outs[-1]] + libs, check=True, env=env, timeout=300)
         a, b = np.load(outs[0]), np.load(outs[1])
@@ -163,7 +191,7 @@ def queries(dirs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("libs", nargs=2)
-    ap.add_argument("--queries", action="store_true", help="libs are two directories, each with the two query libraries")
+    ap.add_argument("--queries", action="store_true", help="libs are two directories, each with the query libraries")
     ap.add_argument("--lying", action="store_true")
     ap.add_argument("--fused", action="store_true")
     ap.add_argument("--config", default="imitation")
