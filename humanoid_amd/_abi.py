@@ -1,16 +1,23 @@
 """ctypes mirrors of ``include/humanoid_engine.h`` and helpers to fill them.
 
 Pure data-contract code: the product shim (``engine.py``) and the test-side oracle wrapper
-(``oracle/oracle.py``) both use these layouts. The three bindings (``engine.py``, ``render.py``,
-``dynamics.py``) also share the library loader and the tensor check here.
+(``oracle/oracle.py``) both use these layouts. The bindings (``engine.py``, ``render.py``,
+``dynamics.py``, ``solve.py``, ``task.py``) also share here the library loader with its return-code
+check (:class:`Library`), the tensor check and, the last three, their base class
+(:class:`QueryBinding`).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
 from .model import HumanoidModel
 
-NB, ND, NG = 24, 69, 75
+NB, ND, NG = 24, 69, 75  # NG = HE_NUM_GEN: 6 root + 69 dof generalised velocities
+# the flags of the query libraries (include/humanoid_dynamics.h, humanoid_solve.h, humanoid_task.h: HD_ /
+# HS_ / HT_FLAG_*, the same bits in all three)
+FLAG_ARMATURE, FLAG_NO_GRAVITY = 1, 2
+FLAGS_DEFAULT = FLAG_ARMATURE
 MAX_PAIRS = 256
 OBS_SELF, OBS_TASK, OBS_DIM = 358, 576, 934
 
@@ -74,6 +81,38 @@ def bind_library(path, prototypes):
     return lib
 
 
+class Library:
+    """One C-ABI library of the package: where it lies, its prototype table, the prefix of its symbols
+    (``"he"``, ``"hr"``, ``"hd"``, ``"hs"``, ``"ht"``) and the error class its binding raises. ``env``
+    names an environment variable that may point at another build (diagnostics only)."""
+
+    def __init__(self, path, prototypes, prefix, error_cls, env=None):
+        self.path, self.prototypes, self.prefix, self.error_cls, self.env = path, prototypes, prefix, error_cls, env
+        self.lib = None
+
+    def load(self, path=None):
+        """Load (never build) the library, once: the first load is the one that stays. It loads without a GPU."""
+        if self.lib is None:
+            p = path or (self.env and os.environ.get(self.env)) or self.path
+            if not os.path.exists(p):
+                raise self.error_cls(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
+            self.lib = bind_library(p, self.prototypes)
+        return self.lib
+
+    def check(self, rc):
+        """A nonzero return code raises the error class with ``<prefix>_last_error``'s text."""
+        if rc != 0:
+            raise self.error_cls(getattr(self.lib, self.prefix + "_last_error")().decode())
+
+    def validate_model(self, he_model):
+        """The host-side model check of ``<prefix>_create`` (``<prefix>_validate_model``); raises the error class."""
+        self.check(getattr(self.load(), self.prefix + "_validate_model")(C.byref(he_model)))
+
+    def check_tensor(self, t, dtype, shape, device, what, at_least=None):
+        """:func:`check_tensor` raising the error class."""
+        return check_tensor(t, dtype, shape, device, what, self.error_cls, at_least)
+
+
 def destroy_handle(obj, destroy):
     """The ``__del__`` of a binding object: its handle ``obj.h`` goes to the library's ``destroy`` once.
     Never raises (the interpreter may be shutting down)."""
@@ -105,6 +144,59 @@ def check_tensor(t, dtype, shape, device, what, error_cls, at_least=None):
                         f"{'contiguous' if t.is_contiguous() else 'non-contiguous'} {t.dtype} {tuple(t.shape)} "
                         f"on {t.device}")
     return C.c_void_p(t.data_ptr())
+
+
+class QueryBinding:
+    """What the bindings of the query libraries (``dynamics.Dynamics``, ``solve.Solver``,
+    ``task.TaskSpace``) share: an object on one engine that owns a library handle made from the engine's
+    model and gravity, launches on the engine's stream and reads the engine's live state unless a call
+    names another. A subclass states ``LIBRARY`` (its :class:`Library`) and ``NO_CPU_PATH`` (the end of
+    the constructor's refusal without a device) and adds the calls that are its own."""
+    LIBRARY = None
+    NO_CPU_PATH = None
+
+    def __init__(self, engine, armature: bool = True):
+        import torch
+        lib = self.LIBRARY
+        self.lib = lib.load()
+        if not torch.cuda.is_available():
+            raise lib.error_cls(f"no HIP device visible: {self.NO_CPU_PATH}")
+        self.engine = engine  # keeps the engine (and the buffers the kernels read) alive
+        self.device = engine.device
+        self.num_envs = engine.num_envs
+        self.armature = bool(armature)
+        self.gravity = True
+        g = (C.c_float * 3)(*[float(x) for x in engine.params.gravity])
+        h = C.c_void_p()
+        create = getattr(self.lib, lib.prefix + "_create")
+        lib.check(create(engine.device_index, C.byref(engine.he_model), g, self.num_envs, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        destroy_handle(self, self.LIBRARY.prefix + "_destroy")
+
+    @property
+    def flags(self) -> int:
+        return (FLAG_ARMATURE if self.armature else 0) | (0 if self.gravity else FLAG_NO_GRAVITY)
+
+    def _flags(self, flags):
+        return int(self.flags if flags is None else flags)
+
+    def _states(self, root_state, dof_state):
+        """The pointers of the checked state tensors; the engine's live buffers where None is given."""
+        import torch
+        n = self.num_envs
+        root = self.engine.root_states if root_state is None else root_state
+        dof = self.engine.dof_state if dof_state is None else dof_state
+        return (self.LIBRARY.check_tensor(root, torch.float32, (n, 13), self.device, "root_state"),
+                self.LIBRARY.check_tensor(dof, torch.float32, (n * ND, 2), self.device, "dof_state"))
+
+    def _out(self, t, shape, what):
+        """The pointer of a checked caller tensor, or of a fresh one: (tensor, pointer)."""
+        import torch
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=self.device)
+        return t, self.LIBRARY.check_tensor(t, torch.float32, shape, self.device, what)
 
 
 class HeModel(C.Structure):

@@ -62,10 +62,7 @@ HEADERS = sorted(os.path.relpath(h, CSRC) for d in (CSRC, os.path.join(HERE, "..
 # (library, its sources, extra flags by source): a source with extra flags gets an object of its own
 # (<source>.phases.o), every other object is shared with the library that built it first
 LIBRARIES = [(LIB, SOURCES, {}), (PHASES_LIB, SOURCES, PHASES_DEFS), (RENDER_LIB, RENDER_SOURCES, {}),
-             (DYNAMICS_LIB, DYNAMICS_SOURCES, {}), (SOLVE_LIB, SOLVE_SOURCES, {})]
-# libraries added since the list above was pinned by the tests of the first five: built after them, by the
-# same rules (compile_command looks their sources' flags up too)
-EXTENSION_LIBRARIES = [(TASK_LIB, TASK_SOURCES, {})]
+             (DYNAMICS_LIB, DYNAMICS_SOURCES, {}), (SOLVE_LIB, SOLVE_SOURCES, {}), (TASK_LIB, TASK_SOURCES, {})]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -83,7 +80,7 @@ def compile_command(src, extra=(), device_only=False, out=None):
     path to a copy elsewhere (flags and id follow the file name). device_only: the gfx950 code object
     alone, for the tools that hash or disassemble it. out: the object, by default _build/<name>.o."""
     name = os.path.basename(src)
-    flags = {s: f for _, sources, _ in LIBRARIES + EXTENSION_LIBRARIES for s, f in sources}[name]
+    flags = {s: f for _, sources, _ in LIBRARIES for s, f in sources}[name]
     # hipcc's default compilation-unit id hashes the source's absolute path into the device
     # symbols of every anonymous-namespace kernel, so device_code_id() would follow the
     # checkout directory; an id from the file name keeps it equal in every checkout
@@ -238,7 +235,7 @@ def build(force=False, verbose=False):
     os.makedirs(BUILD, exist_ok=True)
     hipcc = _hipcc()
     hdr_time = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
-    for lib, sources, defs in LIBRARIES + EXTENSION_LIBRARIES:
+    for lib, sources, defs in LIBRARIES:
         objs = []
         for src, _ in sources:
             o = os.path.join(BUILD, src + (".phases.o" if src in defs else ".o"))

@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <memory>
 
 #include "../../include/humanoid_dynamics.h"
 #include "he_host.h"
@@ -209,11 +208,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 
 }  // namespace
 
-struct hd_dynamics {
-    int device = 0;
-    int num_envs = 0;
-    DeviceArray<TreeModel> d_model;
-};
+struct hd_dynamics : QueryHandle<TreeModel> {};
 
 extern "C" {
 
@@ -226,37 +221,17 @@ int hd_validate_model(const he_model* model) {
 }
 
 int hd_create(int device, const he_model* model, const float gravity[3], int num_envs, hd_dynamics** out) {
-    if (!out) return fail("hd_create: null output pointer");
-    *out = nullptr;
-    if (num_envs < 1) return fail("hd_create: num_envs %d < 1", num_envs);
-    if (!gravity) return fail("hd_create: null gravity vector");
-    if (hd_validate_model(model)) return 1;
-    TreeModel dm;
-    fill_tree_model(model, gravity, dm);
-    if (select_device(device, "hd_create")) return 1;
-    std::unique_ptr<hd_dynamics> h(new hd_dynamics);  // a failed step below frees it and its array
-    h->device = device;
-    h->num_envs = num_envs;
-    HE_CHECK(h->d_model.assign(&dm, 1));
-    *out = h.release();
-    return 0;
+    return query_create("hd_create", device, model, gravity, num_envs, out, hd_validate_model, fill_tree_model);
 }
 
-int hd_destroy(hd_dynamics* h) {
-    if (!h) return 0;
-    (void)hipSetDevice(h->device);
-    delete h;
-    return 0;
-}
+int hd_destroy(hd_dynamics* h) { return query_destroy(h); }
 
 int hd_compute(hd_dynamics* h, const float* root_state, const float* dof_state, float* jac_out, float* mass_out,
                float* bias_out, uint32_t flags, void* stream) {
-    if (!h) return fail("hd_compute: null handle");
-    if (!root_state || !dof_state) return fail("hd_compute: null state pointer");
+    if (check_call("hd_compute", h, root_state, dof_state)) return 1;
     if (!jac_out && !mass_out && !bias_out) return fail("hd_compute: no output buffer");
-    if (flags & ~HD_FLAGS_ALL) return fail("hd_compute: unknown flag bits 0x%x", flags & ~HD_FLAGS_ALL);
-    if (misaligned({root_state, dof_state, jac_out, mass_out, bias_out}))
-        return fail("hd_compute: every buffer must be 4-byte aligned");
+    if (check_flags("hd_compute", flags, HD_FLAGS_ALL)) return 1;
+    if (check_aligned("hd_compute", {root_state, dof_state, jac_out, mass_out, bias_out})) return 1;
     Params P{};
     P.model = h->d_model;
     P.root = root_state;

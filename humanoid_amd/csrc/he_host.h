@@ -1,7 +1,9 @@
-// he_host.h -- the host layer shared by the four C-ABI libraries (engine, renderer, dynamics, solves):
-// the error text, the HIP call check, device selection, the buffer alignment check, the structural
-// he_model check and the owning device array. Host code only, and nothing but the HIP runtime API and the standard library, so a
-// plain C++ compiler builds it (tests/host/ does, against a counting allocator, under a sanitizer).
+// he_host.h -- the host layer shared by the C-ABI libraries (engine, renderer and the query libraries:
+// dynamics, solves, task): the error text, the HIP call check, device selection, the buffer alignment
+// check, the structural he_model check and the owning device array; then what the query libraries share
+// beyond that, their handle, its creation and destruction and the refusals every call of theirs makes.
+// Host code only, and nothing but the HIP runtime API and the standard library, so a plain C++ compiler
+// builds it (tests/host/ does, against a counting allocator, under a sanitizer).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -10,10 +12,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <initializer_list>
+#include <memory>
 #include <string>
 
 // Everything here has internal linkage: each library keeps an error text of its own, also when all
-// four are loaded into one process. A library made of several translation units includes this
+// of them are loaded into one process. A library made of several translation units includes this
 // header in one of them and hands the others a function (the engine: he_fail_text).
 namespace {
 
@@ -135,5 +138,65 @@ public:
     T* get() const { return static_cast<T*>(DeviceBytes::get()); }
     operator T*() const { return get(); }
 };
+
+// ---- the query libraries (hd_dynamics.hip, hs_solve.hip, ht_task.hip): each answers questions about
+// the engine's current state with one kernel that reads a device copy of the model. What follows knows
+// neither the model nor the kernels: the library hands in its model check and the fill of its device model.
+
+// what a query handle holds; a library's handle derives from it and adds what is its own
+template <class DeviceModel>
+struct QueryHandle {
+    using Model = DeviceModel;
+    int device = 0;
+    int num_envs = 0;
+    DeviceArray<DeviceModel> d_model;
+};
+
+// h?_create. validate(model): the library's h?_validate_model; fill(model, gravity, dm): a validated
+// model as the kernel reads it. *out is null on every failure.
+template <class Handle, class HostModel, class Validate, class Fill>
+int query_create(const char* who, int device, const HostModel* model, const float gravity[3], int num_envs, Handle** out,
+                 Validate validate, Fill fill) {
+    if (!out) return fail("%s: null output pointer", who);
+    *out = nullptr;
+    if (num_envs < 1) return fail("%s: num_envs %d < 1", who, num_envs);
+    if (!gravity) return fail("%s: null gravity vector", who);
+    if (validate(model)) return 1;
+    typename Handle::Model dm;
+    fill(model, gravity, dm);
+    if (select_device(device, who)) return 1;
+    std::unique_ptr<Handle> h(new Handle);  // a failed step below frees it and its array
+    h->device = device;
+    h->num_envs = num_envs;
+    HE_CHECK(h->d_model.assign(&dm, 1));
+    *out = h.release();
+    return 0;
+}
+
+// h?_destroy
+template <class Handle>
+int query_destroy(Handle* h) {
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    delete h;
+    return 0;
+}
+
+// The refusals every query call makes, in the order the public headers list them: handle and state
+// pointers first, flags and alignment last. Three pieces, because an entry point's own refusals (a null
+// right-hand side, no output buffer, the mode) sit between them and keep their place.
+int check_call(const char* who, const void* handle, const void* root_state, const void* dof_state) {
+    if (!handle) return fail("%s: null handle", who);
+    if (!root_state || !dof_state) return fail("%s: null state pointer", who);
+    return 0;
+}
+int check_flags(const char* who, uint32_t flags, uint32_t all) {
+    if (flags & ~all) return fail("%s: unknown flag bits 0x%x", who, flags & ~all);
+    return 0;
+}
+int check_aligned(const char* who, std::initializer_list<const void*> buffers) {
+    if (misaligned(buffers)) return fail("%s: every buffer must be 4-byte aligned", who);
+    return 0;
+}
 
 }  // namespace

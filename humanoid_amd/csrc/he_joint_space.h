@@ -181,4 +181,13 @@ __device__ __forceinline__ void crba_row(regla::RegMat& H, const Lds& L, const C
     __builtin_amdgcn_sched_barrier(0);  // row by row: hoisting all 75 broadcasts costs 450 registers
 }
 
+// the factorisation's own demand on a model that passed check_tree_depth: its register indices are this tree's
+int check_factored_tree(const he_model* model) {
+    for (int b = 0; b < NB; ++b)
+        if (model->parents[b] != smpl::kParentBody[b])
+            return fail("model: body %d hangs on body %d; the factorisation is unrolled for a tree where it hangs on %d", b,
+                        model->parents[b], smpl::kParentBody[b]);
+    return 0;
+}
+
 }  // namespace

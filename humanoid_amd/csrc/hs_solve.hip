@@ -23,7 +23,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <type_traits>
 
 #include "../../include/humanoid_solve.h"
@@ -176,11 +175,25 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
 
 }  // namespace
 
-struct hs_solver {
-    int device = 0;
-    int num_envs = 0;
-    DeviceArray<TreeModel> d_model;
-};
+struct hs_solver : QueryHandle<TreeModel> {};
+
+namespace {
+
+// The refusals the three entry points share, in the order the header lists them, around `own`, the
+// entry point's own; then the launch. Every buffer of the call is in P; the handle is read last.
+template <class Own>
+int launch(hs_solver* h, const char* who, void (*kernel)(Params), Params& P, void* stream, Own own) {
+    if (check_call(who, h, P.root, P.dof)) return 1;
+    if (own()) return 1;
+    if (check_flags(who, P.flags, HS_FLAGS_ALL)) return 1;
+    if (check_aligned(who, {P.root, P.dof, P.gen_force, P.qdd_des, P.rhs, P.out, P.base_acc})) return 1;
+    P.model = h->d_model;
+    hipLaunchKernelGGL(kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
+    HE_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -190,69 +203,31 @@ int hs_version(void) { return 1; }
 int hs_validate_model(const he_model* model) {
     if (check_model(model, "model", HE_MAX_BOXES)) return 1;
     if (check_tree_depth(model)) return 1;
-    for (int b = 0; b < NB; ++b)  // the factorisation's register indices are this tree's
-        if (model->parents[b] != smpl::kParentBody[b])
-            return fail("model: body %d hangs on body %d; the factorisation is unrolled for a tree where it hangs on %d", b,
-                        model->parents[b], smpl::kParentBody[b]);
-    return 0;
+    return check_factored_tree(model);
 }
 
 int hs_create(int device, const he_model* model, const float gravity[3], int num_envs, hs_solver** out) {
-    if (!out) return fail("hs_create: null output pointer");
-    *out = nullptr;
-    if (num_envs < 1) return fail("hs_create: num_envs %d < 1", num_envs);
-    if (!gravity) return fail("hs_create: null gravity vector");
-    if (hs_validate_model(model)) return 1;
-    TreeModel dm;
-    fill_tree_model(model, gravity, dm);
-    if (select_device(device, "hs_create")) return 1;
-    std::unique_ptr<hs_solver> h(new hs_solver);  // a failed step below frees it and its array
-    h->device = device;
-    h->num_envs = num_envs;
-    HE_CHECK(h->d_model.assign(&dm, 1));
-    *out = h.release();
-    return 0;
+    return query_create("hs_create", device, model, gravity, num_envs, out, hs_validate_model, fill_tree_model);
 }
 
-int hs_destroy(hs_solver* h) {
-    if (!h) return 0;
-    (void)hipSetDevice(h->device);
-    delete h;
-    return 0;
-}
+int hs_destroy(hs_solver* h) { return query_destroy(h); }
 
 int hs_forward_dynamics(hs_solver* h, const float* root_state, const float* dof_state, const float* gen_force,
                         float* qdd_out, uint32_t flags, void* stream) {
-    if (!h) return fail("hs_forward_dynamics: null handle");
-    if (!root_state || !dof_state) return fail("hs_forward_dynamics: null state pointer");
-    if (!qdd_out) return fail("hs_forward_dynamics: null output buffer");
-    if (flags & ~HS_FLAGS_ALL) return fail("hs_forward_dynamics: unknown flag bits 0x%x", flags & ~HS_FLAGS_ALL);
-    if (misaligned({root_state, dof_state, gen_force, qdd_out}))
-        return fail("hs_forward_dynamics: every buffer must be 4-byte aligned");
     Params P{};
-    P.model = h->d_model;
     P.root = root_state;
     P.dof = dof_state;
     P.gen_force = gen_force;
     P.out = qdd_out;
     P.k = 0;
     P.flags = flags;
-    hipLaunchKernelGGL(solve_kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
-    HE_CHECK(hipGetLastError());
-    return 0;
+    return launch(h, "hs_forward_dynamics", solve_kernel, P, stream,
+                  [&] { return qdd_out ? 0 : fail("hs_forward_dynamics: null output buffer"); });
 }
 
 int hs_computed_torque(hs_solver* h, const float* root_state, const float* dof_state, const float* qdd_des,
                        const float* gen_force, float* tau_out, float* base_acc_out, uint32_t flags, void* stream) {
-    if (!h) return fail("hs_computed_torque: null handle");
-    if (!root_state || !dof_state) return fail("hs_computed_torque: null state pointer");
-    if (!qdd_des) return fail("hs_computed_torque: null desired acceleration");
-    if (!tau_out && !base_acc_out) return fail("hs_computed_torque: no output buffer");
-    if (flags & ~HS_FLAGS_ALL) return fail("hs_computed_torque: unknown flag bits 0x%x", flags & ~HS_FLAGS_ALL);
-    if (misaligned({root_state, dof_state, qdd_des, gen_force, tau_out, base_acc_out}))
-        return fail("hs_computed_torque: every buffer must be 4-byte aligned");
     Params P{};
-    P.model = h->d_model;
     P.root = root_state;
     P.dof = dof_state;
     P.qdd_des = qdd_des;
@@ -260,32 +235,29 @@ int hs_computed_torque(hs_solver* h, const float* root_state, const float* dof_s
     P.out = tau_out;
     P.base_acc = base_acc_out;
     P.flags = flags;
-    hipLaunchKernelGGL(torque_kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
-    HE_CHECK(hipGetLastError());
-    return 0;
+    return launch(h, "hs_computed_torque", torque_kernel, P, stream, [&] {
+        if (!qdd_des) return fail("hs_computed_torque: null desired acceleration");
+        if (!tau_out && !base_acc_out) return fail("hs_computed_torque: no output buffer");
+        return 0;
+    });
 }
 
 int hs_solve(hs_solver* h, const float* root_state, const float* dof_state, const float* rhs, float* out, int k,
              uint32_t flags, void* stream) {
-    if (!h) return fail("hs_solve: null handle");
-    if (!root_state || !dof_state) return fail("hs_solve: null state pointer");
-    if (!rhs) return fail("hs_solve: null right-hand side");
-    if (!out) return fail("hs_solve: null output buffer");
-    if (rhs == out) return fail("hs_solve: rhs and out are the same buffer (the solve is not in place)");
-    if (k < 1 || k > HS_MAX_RHS) return fail("hs_solve: k = %d outside 1..%d", k, HS_MAX_RHS);
-    if (flags & ~HS_FLAGS_ALL) return fail("hs_solve: unknown flag bits 0x%x", flags & ~HS_FLAGS_ALL);
-    if (misaligned({root_state, dof_state, rhs, out})) return fail("hs_solve: every buffer must be 4-byte aligned");
     Params P{};
-    P.model = h->d_model;
     P.root = root_state;
     P.dof = dof_state;
     P.rhs = rhs;
     P.out = out;
     P.k = k;
     P.flags = flags;
-    hipLaunchKernelGGL(solve_kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
-    HE_CHECK(hipGetLastError());
-    return 0;
+    return launch(h, "hs_solve", solve_kernel, P, stream, [&] {
+        if (!rhs) return fail("hs_solve: null right-hand side");
+        if (!out) return fail("hs_solve: null output buffer");
+        if (rhs == out) return fail("hs_solve: rhs and out are the same buffer (the solve is not in place)");
+        if (k < 1 || k > HS_MAX_RHS) return fail("hs_solve: k = %d outside 1..%d", k, HS_MAX_RHS);
+        return 0;
+    });
 }
 
 }  // extern "C"

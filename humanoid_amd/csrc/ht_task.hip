@@ -23,7 +23,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <memory>
 
 #include "../../include/humanoid_task.h"
 #include "he_host.h"
@@ -273,28 +272,25 @@ __global__ __launch_bounds__(kWave, 2) void task_kernel(const Params P) {
 
 }  // namespace
 
-struct ht_task {
-    int device = 0;
-    int num_envs = 0;
+struct ht_task : QueryHandle<TreeModel> {
     int k = 0;  // 0: no rows yet
     ht_row rows[HT_MAX_ROWS] = {};
-    DeviceArray<TreeModel> d_model;
 };
 
 namespace {
 
-// the checks the two entry points share, in the order the header lists them; the handle is read last
+// the checks the two entry points share, in the order the header lists them: the query libraries'
+// (he_host.h) with the task's own in between; the handle is read last
 int launch(ht_task* h, const char* who, Params& P, std::initializer_list<const void*> buffers, bool any_output,
            void* stream) {
-    if (!h) return fail("%s: null handle", who);
-    if (!P.root || !P.dof) return fail("%s: null state pointer", who);
+    if (check_call(who, h, P.root, P.dof)) return 1;
     if (P.control && !P.xdd_des) return fail("%s: null desired acceleration", who);
     if (!any_output) return fail("%s: no output buffer", who);
-    if (P.flags & ~HT_FLAGS_ALL) return fail("%s: unknown flag bits 0x%x", who, P.flags & ~HT_FLAGS_ALL);
+    if (check_flags(who, P.flags, HT_FLAGS_ALL)) return 1;
     if (P.mode != HT_MODE_FORCE && P.mode != HT_MODE_JOINT) return fail("%s: unknown mode %d", who, P.mode);
     if (!(P.damping >= 0.f) || !std::isfinite(P.damping))
         return fail("%s: damping %g is negative or not finite", who, (double)P.damping);
-    if (misaligned(buffers)) return fail("%s: every buffer must be 4-byte aligned", who);
+    if (check_aligned(who, buffers)) return 1;
     if (h->k < 1) return fail("%s: no rows set (ht_set_rows)", who);
     P.model = h->d_model;
     P.k = h->k;
@@ -315,36 +311,14 @@ int ht_version(void) { return 1; }
 int ht_validate_model(const he_model* model) {
     if (check_model(model, "model", HE_MAX_BOXES)) return 1;
     if (check_tree_depth(model)) return 1;
-    for (int b = 0; b < NB; ++b)  // the factorisation's register indices are this tree's
-        if (model->parents[b] != smpl::kParentBody[b])
-            return fail("model: body %d hangs on body %d; the factorisation is unrolled for a tree where it hangs on %d", b,
-                        model->parents[b], smpl::kParentBody[b]);
-    return 0;
+    return check_factored_tree(model);
 }
 
 int ht_create(int device, const he_model* model, const float gravity[3], int num_envs, ht_task** out) {
-    if (!out) return fail("ht_create: null output pointer");
-    *out = nullptr;
-    if (num_envs < 1) return fail("ht_create: num_envs %d < 1", num_envs);
-    if (!gravity) return fail("ht_create: null gravity vector");
-    if (ht_validate_model(model)) return 1;
-    TreeModel dm;
-    fill_tree_model(model, gravity, dm);
-    if (select_device(device, "ht_create")) return 1;
-    std::unique_ptr<ht_task> h(new ht_task);  // a failed step below frees it and its array
-    h->device = device;
-    h->num_envs = num_envs;
-    HE_CHECK(h->d_model.assign(&dm, 1));
-    *out = h.release();
-    return 0;
+    return query_create("ht_create", device, model, gravity, num_envs, out, ht_validate_model, fill_tree_model);
 }
 
-int ht_destroy(ht_task* h) {
-    if (!h) return 0;
-    (void)hipSetDevice(h->device);
-    delete h;
-    return 0;
-}
+int ht_destroy(ht_task* h) { return query_destroy(h); }
 
 int ht_set_rows(ht_task* h, const ht_row* rows, int k) {
     if (!h) return fail("ht_set_rows: null handle");

@@ -19,14 +19,10 @@ from typing import Optional
 
 from . import _abi
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_dynamics.so")
-_lib = None
+from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_dynamics.h)
 
-# include/humanoid_dynamics.h
-FLAG_ARMATURE, FLAG_NO_GRAVITY = 1, 2
-FLAGS_DEFAULT = FLAG_ARMATURE
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_dynamics.so")
 JAC_ROWS = 6
-NG = 75  # HE_NUM_GEN: 6 root + 69 dof generalised velocities
 
 _V, _I = C.c_void_p, C.c_int
 # every exported symbol with its prototype (_abi.bind_library)
@@ -41,31 +37,10 @@ class DynamicsError(RuntimeError):
     pass
 
 
-def load_library(path: Optional[str] = None):
-    """Load (never build) the dynamics library; it loads without a GPU."""
-    global _lib
-    if _lib is None:
-        p = path or LIB_PATH
-        if not os.path.exists(p):
-            raise DynamicsError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-        _lib = _abi.bind_library(p, HD_PROTOTYPES)
-    return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise DynamicsError(_lib.hd_last_error().decode())
-
-
-def validate_model(he_model: _abi.HeModel):
-    """The host-side model check of hd_create (hd_validate_model); raises :class:`DynamicsError`."""
-    lib = load_library()
-    _check(lib.hd_validate_model(C.byref(he_model)))
-
-
-def check_tensor(t, dtype, shape, device, what):
-    """_abi.check_tensor raising :class:`DynamicsError`."""
-    return _abi.check_tensor(t, dtype, shape, device, what, DynamicsError)
+# load (never build) the library, a return code, hd_validate_model and _abi.check_tensor, raising DynamicsError
+_LIBRARY = _abi.Library(LIB_PATH, HD_PROTOTYPES, "hd", DynamicsError)
+load_library, _check, validate_model, check_tensor = (_LIBRARY.load, _LIBRARY.check, _LIBRARY.validate_model,
+                                                      _LIBRARY.check_tensor)
 
 
 def output_shapes(num_envs: int):
@@ -73,7 +48,7 @@ def output_shapes(num_envs: int):
     return {"jacobian": (n, _abi.NB, JAC_ROWS, NG), "mass_matrix": (n, NG, NG), "bias": (n, NG)}
 
 
-class Dynamics:
+class Dynamics(_abi.QueryBinding):
     """The dynamics-query tensors of one :class:`humanoid_amd.engine.Engine`.
 
     ``jacobian`` f32 [N,24,6,75] (rows: body-origin linear velocity, world angular velocity),
@@ -82,20 +57,11 @@ class Dynamics:
     model's dof armature on the mass matrix's diagonal; ``gravity`` (default on) keeps gravity in the
     bias force. Gravity is the engine's ``sim_params.gravity``."""
 
+    LIBRARY, NO_CPU_PATH = _LIBRARY, "the dynamics kernel has no CPU path"
+
     def __init__(self, engine, armature: bool = True):
         import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise DynamicsError("no HIP device visible: the dynamics kernel has no CPU path")
-        self.engine = engine  # keeps the engine (and the buffers the kernel reads) alive
-        self.device = engine.device
-        self.num_envs = engine.num_envs
-        self.armature = bool(armature)
-        self.gravity = True
-        g = (C.c_float * 3)(*[float(x) for x in engine.params.gravity])
-        h = C.c_void_p()
-        _check(self.lib.hd_create(engine.device_index, C.byref(engine.he_model), g, self.num_envs, C.byref(h)))
-        self.h = h
+        super().__init__(engine, armature)
         shapes = output_shapes(self.num_envs)
         self.jacobian = torch.zeros(shapes["jacobian"], dtype=torch.float32, device=self.device)
         self.mass_matrix = torch.zeros(shapes["mass_matrix"], dtype=torch.float32, device=self.device)
@@ -103,21 +69,13 @@ class Dynamics:
         self._solver = None  # humanoid_amd.solve.Solver, created by the first solve
         self._task = None  # humanoid_amd.task.TaskSpace, created by the first use
 
-    def __del__(self):
-        _abi.destroy_handle(self, "hd_destroy")
-
-    @property
-    def flags(self) -> int:
-        return (FLAG_ARMATURE if self.armature else 0) | (0 if self.gravity else FLAG_NO_GRAVITY)
-
     def refresh_into(self, jacobian=None, mass_matrix=None, bias=None, flags: Optional[int] = None, root_state=None,
                      dof_state=None):
         """hd_compute into caller tensors (``None``: that output is not computed). The states default to
         the engine's live root-state / dof-state buffers. Every tensor is checked (shape, dtype, device,
         contiguity) before any pointer is passed."""
         import torch
-        n = self.num_envs
-        shapes = output_shapes(n)
+        shapes = output_shapes(self.num_envs)
         if jacobian is None and mass_matrix is None and bias is None:
             raise DynamicsError("refresh: no output asked for")
         f32 = torch.float32
@@ -125,12 +83,8 @@ class Dynamics:
         p_mass = None if mass_matrix is None else check_tensor(mass_matrix, f32, shapes["mass_matrix"], self.device,
                                                                "mass_matrix")
         p_bias = None if bias is None else check_tensor(bias, f32, shapes["bias"], self.device, "bias")
-        root = self.engine.root_states if root_state is None else root_state
-        dof = self.engine.dof_state if dof_state is None else dof_state
-        p_root = check_tensor(root, f32, (n, 13), self.device, "root_state")
-        p_dof = check_tensor(dof, f32, (n * _abi.ND, 2), self.device, "dof_state")
-        _check(self.lib.hd_compute(self.h, p_root, p_dof, p_jac, p_mass, p_bias,
-                                   int(self.flags if flags is None else flags), self.engine.stream))
+        p_root, p_dof = self._states(root_state, dof_state)
+        _check(self.lib.hd_compute(self.h, p_root, p_dof, p_jac, p_mass, p_bias, self._flags(flags), self.engine.stream))
 
     def refresh(self, jacobian: bool = True, mass_matrix: bool = True, bias: bool = True):
         """Recompute what is asked from the engine's current state: one launch on the current stream, no

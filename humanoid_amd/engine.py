@@ -18,7 +18,6 @@ import numpy as np
 from . import _abi
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_engine.so")
-_lib = None
 
 
 class EngineError(RuntimeError):
@@ -57,21 +56,10 @@ HE_PROTOTYPES = {
 HE_SYMBOLS = tuple(HE_PROTOTYPES)
 
 
-def load_library(path: Optional[str] = None):
-    """Load (never build) the HIP engine library; raise loudly when it is missing."""
-    global _lib
-    if _lib is None:
-        # HE_ENGINE_LIB: diagnostics only (A/B timing of a variant build, tools/build_variant.py)
-        p = path or os.environ.get("HE_ENGINE_LIB") or LIB_PATH
-        if not os.path.exists(p):
-            raise EngineError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-        _lib = _abi.bind_library(p, HE_PROTOTYPES)
-    return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise EngineError(_lib.he_last_error().decode())
+# load (never build) the library and check a return code, raising EngineError. HE_ENGINE_LIB: diagnostics
+# only (A/B timing of a variant build, tools/build_variant.py)
+_LIBRARY = _abi.Library(LIB_PATH, HE_PROTOTYPES, "he", EngineError, env="HE_ENGINE_LIB")
+load_library, _check = _LIBRARY.load, _LIBRARY.check
 
 
 class _CudaArray:
@@ -204,7 +192,7 @@ class Engine:
     def _dev(self, t, dtype, what, shape=None):
         """The device pointer of a contiguous tensor of this dtype (and shape or element count) on the
         engine's device (_abi.check_tensor; gymtorch refused non-contiguous tensors, wrapper.py:47-49)."""
-        return _abi.check_tensor(t, dtype, shape, self.device, what, EngineError)
+        return _LIBRARY.check_tensor(t, dtype, shape, self.device, what)
 
     def set_dof_targets(self, t):
         import torch
@@ -467,7 +455,7 @@ def amp_observations(root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_ve
     ins = (root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, key_body_pos)
     shapes = ((k, 3), (k, 4), (k, 3), (k, 3), (k, 69), (k, 69), (k, 4, 3))
     dev = root_pos.device
-    ptrs = [_abi.check_tensor(t, torch.float32, sh, dev, "he_amp_observations", EngineError)
+    ptrs = [_LIBRARY.check_tensor(t, torch.float32, sh, dev, "he_amp_observations")
             for t, sh in zip(ins, shapes)]
     out = torch.empty(k, _abi.AMP_OBS_STEP, device=dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

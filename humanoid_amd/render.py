@@ -12,14 +12,13 @@ import ctypes as C
 import os
 import struct
 import zlib
-from typing import Optional, Sequence
+from typing import Sequence
 
 import numpy as np
 
 from . import _abi
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_render.so")
-_lib = None
 
 # include/humanoid_render.h
 FLAG_SHADOWS, FLAG_CHECKER, FLAG_NO_CULL = 1, 2, 4
@@ -62,20 +61,9 @@ def camera(env: int, width: int, height: int, pos, target, hfov_deg: float = 90.
     return c
 
 
-def load_library(path: Optional[str] = None):
-    """Load (never build) the render library; it loads without a GPU."""
-    global _lib
-    if _lib is None:
-        p = path or LIB_PATH
-        if not os.path.exists(p):
-            raise RenderError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-        _lib = _abi.bind_library(p, HR_PROTOTYPES)
-    return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise RenderError(_lib.hr_last_error().decode())
+# load (never build) the library and check a return code, raising RenderError
+_LIBRARY = _abi.Library(LIB_PATH, HR_PROTOTYPES, "hr", RenderError)
+load_library, _check = _LIBRARY.load, _LIBRARY.check
 
 
 def validate_cameras(cams: Sequence[HrCamera], num_envs: int):
@@ -113,7 +101,7 @@ class Renderer:
         _abi.destroy_handle(self, "hr_destroy")
 
     def _dev(self, t, dtype, shape, what, at_least=None):
-        return _abi.check_tensor(t, dtype, shape, self.device, what, RenderError, at_least)
+        return _LIBRARY.check_tensor(t, dtype, shape, self.device, what, at_least)
 
     def set_cameras(self, cams: Sequence[HrCamera]):
         """Replace the camera set (all of one size). A refused set raises and leaves the previous one."""

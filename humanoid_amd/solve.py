@@ -21,14 +21,10 @@ from typing import Optional
 
 from . import _abi
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_solve.so")
-_lib = None
+from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_solve.h)
 
-# include/humanoid_solve.h
-FLAG_ARMATURE, FLAG_NO_GRAVITY = 1, 2
-FLAGS_DEFAULT = FLAG_ARMATURE
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_solve.so")
 MAX_RHS = 32
-NG = 75  # HE_NUM_GEN: 6 root + 69 dof generalised velocities
 
 _V, _I, _U = C.c_void_p, C.c_int, C.c_uint32
 # every exported symbol with its prototype (_abi.bind_library)
@@ -44,34 +40,13 @@ class SolveError(RuntimeError):
     pass
 
 
-def load_library(path: Optional[str] = None):
-    """Load (never build) the solve library; it loads without a GPU."""
-    global _lib
-    if _lib is None:
-        p = path or LIB_PATH
-        if not os.path.exists(p):
-            raise SolveError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-        _lib = _abi.bind_library(p, HS_PROTOTYPES)
-    return _lib
+# load (never build) the library, a return code, hs_validate_model and _abi.check_tensor, raising SolveError
+_LIBRARY = _abi.Library(LIB_PATH, HS_PROTOTYPES, "hs", SolveError)
+load_library, _check, validate_model, check_tensor = (_LIBRARY.load, _LIBRARY.check, _LIBRARY.validate_model,
+                                                      _LIBRARY.check_tensor)
 
 
-def _check(rc):
-    if rc != 0:
-        raise SolveError(_lib.hs_last_error().decode())
-
-
-def validate_model(he_model: _abi.HeModel):
-    """The host-side model check of hs_create (hs_validate_model); raises :class:`SolveError`."""
-    lib = load_library()
-    _check(lib.hs_validate_model(C.byref(he_model)))
-
-
-def check_tensor(t, dtype, shape, device, what):
-    """_abi.check_tensor raising :class:`SolveError`."""
-    return _abi.check_tensor(t, dtype, shape, device, what, SolveError)
-
-
-class Solver:
+class Solver(_abi.QueryBinding):
     """The joint-space solves of one :class:`humanoid_amd.engine.Engine`.
 
     ``armature`` (default on: the inertia the engine's own solve uses) puts the model's dof armature on
@@ -79,45 +54,7 @@ class Solver:
     ``sim_params.gravity``. The states default to the engine's live buffers, every launch goes on the
     engine's stream without synchronising the host, and an ``out`` tensor is allocated when not given."""
 
-    def __init__(self, engine, armature: bool = True):
-        import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise SolveError("no HIP device visible: the solve kernels have no CPU path")
-        self.engine = engine  # keeps the engine (and the buffers the kernels read) alive
-        self.device = engine.device
-        self.num_envs = engine.num_envs
-        self.armature = bool(armature)
-        self.gravity = True
-        g = (C.c_float * 3)(*[float(x) for x in engine.params.gravity])
-        h = C.c_void_p()
-        _check(self.lib.hs_create(engine.device_index, C.byref(engine.he_model), g, self.num_envs, C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        _abi.destroy_handle(self, "hs_destroy")
-
-    @property
-    def flags(self) -> int:
-        return (FLAG_ARMATURE if self.armature else 0) | (0 if self.gravity else FLAG_NO_GRAVITY)
-
-    def _states(self, root_state, dof_state):
-        import torch
-        n = self.num_envs
-        root = self.engine.root_states if root_state is None else root_state
-        dof = self.engine.dof_state if dof_state is None else dof_state
-        return (check_tensor(root, torch.float32, (n, 13), self.device, "root_state"),
-                check_tensor(dof, torch.float32, (n * _abi.ND, 2), self.device, "dof_state"))
-
-    def _out(self, t, shape, what):
-        """The pointer of a checked caller tensor, or of a fresh one: (tensor, pointer)."""
-        import torch
-        if t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=self.device)
-        return t, check_tensor(t, torch.float32, shape, self.device, what)
-
-    def _flags(self, flags):
-        return int(self.flags if flags is None else flags)
+    LIBRARY, NO_CPU_PATH = _LIBRARY, "the solve kernels have no CPU path"
 
     def forward_dynamics(self, gen_force=None, out=None, flags: Optional[int] = None, root_state=None, dof_state=None):
         """qdd [N,75] = M^-1 (gen_force - c); ``gen_force`` [N,75] or None for zero."""

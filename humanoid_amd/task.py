@@ -25,16 +25,12 @@ from typing import Optional
 
 from . import _abi
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_task.so")
-_lib = None
+from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_task.h)
 
-# include/humanoid_task.h
-FLAG_ARMATURE, FLAG_NO_GRAVITY = 1, 2
-FLAGS_DEFAULT = FLAG_ARMATURE
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_task.so")
 MODE_FORCE, MODE_JOINT = 0, 1
 MODES = {"force": MODE_FORCE, "joint": MODE_JOINT}
 MAX_ROWS = 32
-NG = 75  # HE_NUM_GEN: 6 root + 69 dof generalised velocities
 
 
 class HtRow(C.Structure):
@@ -58,31 +54,10 @@ class TaskError(RuntimeError):
     pass
 
 
-def load_library(path: Optional[str] = None):
-    """Load (never build) the task library; it loads without a GPU."""
-    global _lib
-    if _lib is None:
-        p = path or LIB_PATH
-        if not os.path.exists(p):
-            raise TaskError(f"{p} not found: build it with `python -m humanoid_amd.build` (hipcc, gfx950)")
-        _lib = _abi.bind_library(p, HT_PROTOTYPES)
-    return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise TaskError(_lib.ht_last_error().decode())
-
-
-def validate_model(he_model: _abi.HeModel):
-    """The host-side model check of ht_create (ht_validate_model); raises :class:`TaskError`."""
-    lib = load_library()
-    _check(lib.ht_validate_model(C.byref(he_model)))
-
-
-def check_tensor(t, dtype, shape, device, what):
-    """_abi.check_tensor raising :class:`TaskError`."""
-    return _abi.check_tensor(t, dtype, shape, device, what, TaskError)
+# load (never build) the library, a return code, ht_validate_model and _abi.check_tensor, raising TaskError
+_LIBRARY = _abi.Library(LIB_PATH, HT_PROTOTYPES, "ht", TaskError)
+load_library, _check, validate_model, check_tensor = (_LIBRARY.load, _LIBRARY.check, _LIBRARY.validate_model,
+                                                      _LIBRARY.check_tensor)
 
 
 def make_rows(rows):
@@ -107,7 +82,7 @@ def make_rows(rows):
     return arr, len(rows)
 
 
-class TaskSpace:
+class TaskSpace(_abi.QueryBinding):
     """Task-space control on one :class:`humanoid_amd.engine.Engine`.
 
     ``armature`` (default on: the inertia the engine's own solve uses) puts the model's dof armature on
@@ -116,28 +91,11 @@ class TaskSpace:
     default to the engine's live buffers, every launch goes on the engine's stream without synchronising
     the host, and an output tensor is allocated when not given."""
 
+    LIBRARY, NO_CPU_PATH = _LIBRARY, "the task kernel has no CPU path"
+
     def __init__(self, engine, armature: bool = True):
-        import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise TaskError("no HIP device visible: the task kernel has no CPU path")
-        self.engine = engine  # keeps the engine (and the buffers the kernel reads) alive
-        self.device = engine.device
-        self.num_envs = engine.num_envs
-        self.armature = bool(armature)
-        self.gravity = True
         self.num_rows = 0
-        g = (C.c_float * 3)(*[float(x) for x in engine.params.gravity])
-        h = C.c_void_p()
-        _check(self.lib.ht_create(engine.device_index, C.byref(engine.he_model), g, self.num_envs, C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        _abi.destroy_handle(self, "ht_destroy")
-
-    @property
-    def flags(self) -> int:
-        return (FLAG_ARMATURE if self.armature else 0) | (0 if self.gravity else FLAG_NO_GRAVITY)
+        super().__init__(engine, armature)
 
     def set_rows(self, rows):
         """The task rows, ``(body index or name, axis, point=(0, 0, 0))`` each, 1 to 32 of them; they
@@ -146,21 +104,6 @@ class TaskSpace:
         _check(self.lib.ht_set_rows(self.h, arr, k))
         self.num_rows = k
         return k
-
-    def _states(self, root_state, dof_state):
-        import torch
-        n = self.num_envs
-        root = self.engine.root_states if root_state is None else root_state
-        dof = self.engine.dof_state if dof_state is None else dof_state
-        return (check_tensor(root, torch.float32, (n, 13), self.device, "root_state"),
-                check_tensor(dof, torch.float32, (n * _abi.ND, 2), self.device, "dof_state"))
-
-    def _out(self, t, shape, what):
-        """The pointer of a checked caller tensor, or of a fresh one: (tensor, pointer)."""
-        import torch
-        if t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=self.device)
-        return t, check_tensor(t, torch.float32, shape, self.device, what)
 
     def _rows(self, what):
         if self.num_rows < 1:
@@ -191,7 +134,7 @@ class TaskSpace:
             else:
                 ptrs.append(None)
         p_root, p_dof = self._states(root_state, dof_state)
-        _check(self.lib.ht_task_terms(self.h, p_root, p_dof, p_f, *ptrs, int(self.flags if flags is None else flags),
+        _check(self.lib.ht_task_terms(self.h, p_root, p_dof, p_f, *ptrs, self._flags(flags),
                                       self.engine.stream))
         return res
 
@@ -225,5 +168,5 @@ class TaskSpace:
             qdd, p_q = self._out(qdd, (n, NG), "qdd")
         p_root, p_dof = self._states(root_state, dof_state)
         _check(self.lib.ht_task_control(self.h, p_root, p_dof, p_x, p_f, int(mode), damping, p_u, p_tf, p_q,
-                                        int(self.flags if flags is None else flags), self.engine.stream))
+                                        self._flags(flags), self.engine.stream))
         return (out if want_gen_force else None), (task_force if want_task_force else None), (qdd if want_qdd else None)

@@ -1,6 +1,7 @@
-// Ownership of humanoid_amd/csrc/he_host.h's device arrays, on the CPU: this file is the HIP runtime
-// (a counting allocator over malloc that can be told to fail the k-th allocation or the k-th copy), so
-// the program links no HIP and runs under the host compiler's sanitizers (tests/test_host_layer.py).
+// Ownership of humanoid_amd/csrc/he_host.h's device arrays and of the query libraries' handles, on the
+// CPU: this file is the HIP runtime (a counting allocator over malloc that can be told to fail the k-th
+// allocation or the k-th copy), so the program links no HIP and runs under the host compiler's sanitizers
+// (tests/test_host_layer.py).
 #include "he_host.h"
 
 #include <cstdint>
@@ -218,11 +219,87 @@ int test_check_model() {
     return 0;
 }
 
+// the query libraries' create and destroy, with a toy handle, model and checks in the libraries' places
+struct ToyHost {
+    int32_t n;
+};
+struct ToyModel {
+    int32_t n;
+    float gravity[3];
+};
+struct ToyHandle : QueryHandle<ToyModel> {
+    int rows = 7;  // a library's own member
+};
+int toy_validate(const ToyHost* m) { return m && m->n > 0 ? 0 : fail("model: refused by the test"); }
+void toy_fill(const ToyHost* m, const float gravity[3], ToyModel& dm) {
+    dm = ToyModel{m->n, {gravity[0], gravity[1], gravity[2]}};
+}
+int toy_create(int device, const ToyHost* m, const float* gravity, int num_envs, ToyHandle** out) {
+    return query_create("x_create", device, m, gravity, num_envs, out, toy_validate, toy_fill);
+}
+
+int test_query_create_and_destroy() {
+    const ToyHost ok{5}, bad{0};
+    const float g[3] = {0.f, 0.f, -9.81f};
+    ToyHandle* const stale = reinterpret_cast<ToyHandle*>(0x10);  // a failure must not leave it in *out
+    ToyHandle* h = stale;
+    devices = 2;
+    // each argument refusal, in create's order: *out null, nothing allocated
+    reset();
+    EXPECT(toy_create(0, &ok, g, 4, nullptr) == 1 && !std::strcmp(last_error(), "x_create: null output pointer"));
+    EXPECT(toy_create(0, nullptr, nullptr, 0, &h) == 1 && !std::strcmp(last_error(), "x_create: num_envs 0 < 1") && !h);
+    h = stale;
+    EXPECT(toy_create(0, nullptr, nullptr, 4, &h) == 1 && !std::strcmp(last_error(), "x_create: null gravity vector") && !h);
+    h = stale;
+    EXPECT(toy_create(0, &bad, g, 4, &h) == 1 && !std::strcmp(last_error(), "model: refused by the test") && !h);
+    h = stale;
+    EXPECT(toy_create(2, &ok, g, 4, &h) == 1 && !std::strcmp(last_error(), "x_create: device 2 of 2") && !h);
+    devices = 0;
+    h = stale;
+    EXPECT(toy_create(0, &ok, g, 4, &h) == 1 && std::strstr(last_error(), "x_create: no HIP device") && !h);
+    EXPECT(allocs == 0 && frees == 0 && live.empty());
+    devices = 2;
+    // a failed allocation, then a failed copy: the handle and its array are gone
+    reset(0);
+    h = stale;
+    EXPECT(toy_create(1, &ok, g, 4, &h) == 1 && std::strstr(last_error(), "d_model.assign") && !h);
+    EXPECT(allocs == 1 && live.empty() && frees == 0 && bad_frees == 0);
+    reset(-1, 0);
+    h = stale;
+    EXPECT(toy_create(1, &ok, g, 4, &h) == 1 && std::strstr(last_error(), "d_model.assign") && !h);
+    EXPECT(allocs == 1 && copies == 1 && live.empty() && frees == 1 && bad_frees == 0);
+    // success: the handle as asked, the filled model in its array; destroy frees that array, once
+    reset();
+    EXPECT(toy_create(1, &ok, g, 4, &h) == 0 && h && h != stale);
+    EXPECT(h->device == 1 && h->num_envs == 4 && h->rows == 7 && live.size() == 1 && live.count(h->d_model.get()));
+    const ToyModel* dm = h->d_model;
+    EXPECT(last_bytes == sizeof(ToyModel) && dm->n == 5 && dm->gravity[2] == g[2]);
+    EXPECT(query_destroy(h) == 0 && live.empty() && frees == 1 && bad_frees == 0);
+    EXPECT(query_destroy(static_cast<ToyHandle*>(nullptr)) == 0 && frees == 1);
+    return 0;
+}
+
+// the refusals every query call makes, piece by piece
+int test_query_call_checks() {
+    int x[2] = {0, 0};
+    const void* odd = reinterpret_cast<const char*>(x) + 2;
+    EXPECT(check_call("x_call", nullptr, x, x) == 1 && !std::strcmp(last_error(), "x_call: null handle"));
+    EXPECT(check_call("x_call", x, nullptr, x) == 1 && !std::strcmp(last_error(), "x_call: null state pointer"));
+    EXPECT(check_call("x_call", x, x, nullptr) == 1 && !std::strcmp(last_error(), "x_call: null state pointer"));
+    EXPECT(check_call("x_call", x, x, x) == 0);
+    EXPECT(check_flags("x_call", 3u, 3u) == 0);
+    EXPECT(check_flags("x_call", 13u, 3u) == 1 && !std::strcmp(last_error(), "x_call: unknown flag bits 0xc"));
+    EXPECT(check_aligned("x_call", {x, nullptr, x + 1}) == 0);
+    EXPECT(check_aligned("x_call", {x, odd}) == 1 && !std::strcmp(last_error(), "x_call: every buffer must be 4-byte aligned"));
+    return 0;
+}
+
 }  // namespace
 
 int main() {
     if (test_failed_allocation_leaves_nothing() || test_move_assignment_frees_the_replaced_array_once() ||
-        test_staged_replace() || test_zero_length_array() || test_select_device() || test_check_model())
+        test_staged_replace() || test_zero_length_array() || test_select_device() || test_check_model() ||
+        test_query_create_and_destroy() || test_query_call_checks())
         return 1;
     std::puts("he_host ownership: ok");
     return 0;

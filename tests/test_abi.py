@@ -180,7 +180,7 @@ def test_spill_ceilings_read_the_named_kernel():
 
 
 def test_compile_command_is_the_builds():
-    """build.compile_command gives, for every object of the five libraries, the line build() has always
+    """build.compile_command gives, for every object of the six libraries, the line build() has always
     written into the object's .cmd stamp (so a tree built before recompiles nothing for the flags' sake),
     and tools/build_variant.py's line for the physics TU is the product's but for the object."""
     import hashlib
@@ -188,7 +188,7 @@ def test_compile_command_is_the_builds():
     from humanoid_amd import build
     common = ["--offload-arch=" + build.ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
     libraries = [(build.SOURCES, {}), (build.SOURCES, build.PHASES_DEFS), (build.RENDER_SOURCES, {}),
-                 (build.DYNAMICS_SOURCES, {}), (build.SOLVE_SOURCES, {})]
+                 (build.DYNAMICS_SOURCES, {}), (build.SOLVE_SOURCES, {}), (build.TASK_SOURCES, {})]
     assert [s for _, s, _ in build.LIBRARIES] == [s for s, _ in libraries]
     assert [d for _, _, d in build.LIBRARIES] == [d for _, d in libraries]
     n = 0
@@ -199,7 +199,7 @@ def test_compile_command_is_the_builds():
                 defs.get(src, []) + ["-c", os.path.join(build.CSRC, src), "-o", o]
             assert " ".join(build.compile_command(src, defs.get(src, ()), out=o)) == " ".join(want)
             n += 1
-    assert n == 17
+    assert n == 18
     # the physics TU's line spelled out, and the default object
     phys = os.path.join(build.CSRC, "he_physics.hip")
     assert " ".join(build.compile_command("he_physics.hip")) == (

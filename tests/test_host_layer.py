@@ -1,6 +1,7 @@
-"""CPU checks of the host layer the four C-ABI libraries share (humanoid_amd/csrc/he_host.h): the
-owning device arrays under a host sanitizer, as a stand-alone program against a counting allocator
-(tests/host/device_array_test.cpp), and the error text, which each library keeps for itself."""
+"""CPU checks of the host layer the C-ABI libraries share (humanoid_amd/csrc/he_host.h): the owning
+device arrays and the query libraries' create, destroy and call checks under a host sanitizer, as a
+stand-alone program against a counting allocator (tests/host/device_array_test.cpp), and the error
+text, which each library keeps for itself."""
 import ctypes as C
 import os
 import shutil
@@ -23,7 +24,10 @@ def _rocm_include():
 def test_device_arrays_own_their_memory_under_a_sanitizer(tmp_path):
     """he_host.h builds with the plain host compiler, and its arrays free what they hold exactly once on
     every path: a failed k-th allocation of a sequence, move assignment, the staged replace of the motion
-    tables with any step failing, a zero-length array. AddressSanitizer (with its leak check) and UBSan
+    tables with any step failing, a zero-length array. The query libraries' shared create and destroy,
+    with a toy handle and model: every argument refusal leaves the output null and allocates nothing, a
+    failed allocation or copy leaves nothing alive, a created handle is freed once, destroying null is 0;
+    and the refusals their calls share, text by text. AddressSanitizer (with its leak check) and UBSan
     watch the run; the program's own counters are asserted in it."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     assert cxx, "no host C++ compiler"

@@ -77,10 +77,10 @@ def test_task_library_exports_exactly_the_declared_symbols():
 
 def test_task_library_is_an_extension_library_of_its_own():
     from humanoid_amd import build
-    assert [(lib, [s for s, _ in sources]) for lib, sources, _ in build.EXTENSION_LIBRARIES] == \
-        [(build.TASK_LIB, ["ht_task.hip"])]
-    assert build.TASK_LIB not in [lib for lib, _, _ in build.LIBRARIES]
-    assert not [s for _, sources, _ in build.LIBRARIES for s, _ in sources if s.startswith("ht_")]
+    # one entry of the one table, its sources ht_task.hip alone; no other library lists an ht_ source
+    assert [[s for s, _ in sources] for lib, sources, _ in build.LIBRARIES if lib == build.TASK_LIB] == [["ht_task.hip"]]
+    assert not [s for lib, sources, _ in build.LIBRARIES if lib != build.TASK_LIB for s, _ in sources if s.startswith("ht_")]
+    assert len({lib for lib, _, _ in build.LIBRARIES}) == len(build.LIBRARIES) == 6
     assert dict(build.TASK_SOURCES)["ht_task.hip"] == dict(build.SOLVE_SOURCES)["hs_solve.hip"] == ["-fno-slp-vectorize"]
     assert any(h.endswith("humanoid_task.h") for h in build.HEADERS)
     assert any(h.endswith("he_joint_space.h") for h in build.HEADERS)
