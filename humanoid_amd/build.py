@@ -101,12 +101,14 @@ MIN_OCCUPANCY = {"he_physics.hip": ("physics_kernel", 2), "ht_task.hip": ("task_
 # how many kernels of the TU match the watched name (physics_kernel and physics_kernel_tgs): a report
 # that lists fewer fails the build, so neither can drop out of the check unnoticed
 MIN_KERNELS = {"he_physics.hip": 2}
-# kernels that must not touch scratch memory (no spilled registers, no stack): the render kernel keeps
-# its primitives in LDS and everything else in registers; the dynamics kernel keeps its matrices in
+# kernels that must not touch scratch memory (no spilled registers, no stack): the render kernels keep
+# their primitives in LDS and everything else in registers; the dynamics kernel keeps its matrices in
 # named registers and indexes only LDS; the solve kernels (a source names one kernel or a tuple of
-# them) hold the mass matrix and its factorisation in registers, within the 256 of two waves per SIMD
-NO_SCRATCH = {"hr_render.hip": "render_kernel", "hd_dynamics.hip": "dynamics_kernel",
-              "hs_solve.hip": ("solve_kernel", "torque_kernel"), "ht_task.hip": "task_kernel"}
+# them; a template's instantiations by the name with its mangled argument, render_kernel<false> and
+# <true>) hold the mass matrix and its factorisation in registers, within the 256 of two waves per SIMD
+NO_SCRATCH = {"hr_render.hip": ("render_kernelILb0", "render_kernelILb1", "rays_kernel"),
+              "hd_dynamics.hip": "dynamics_kernel", "hs_solve.hip": ("solve_kernel", "torque_kernel"),
+              "ht_task.hip": "task_kernel"}
 # ceilings on the physics kernels' register spills, by exact kernel name: (scratch bytes per lane,
 # spilled VGPRs) of the compiler's resource report, no slack (as the occupancy). The TGS kernel's
 # spills are a plan, not a by-product: what is parked is the <= 32-row class's columns

@@ -7,6 +7,11 @@
 //              pixel loop walks the set bits, so the trip count is the same in all lanes and only the
 //              hit tests diverge. The shadow rays get a second mask over the 24 bodies;
 //   stores     masked (partial tiles run every barrier), one packed 32-bit colour store per pixel.
+// The ground every ray tests first is the env's terrain (hr_set_terrain): its kind is one wave-uniform
+// load in the prologue of render_kernel<true>. A renderer without a kind array launches
+// render_kernel<false>, the same body with the plane fixed at compile time: an unset terrain costs nothing.
+// A second kernel, rays_kernel, is the ray-cast sensor (hr_cast_rays) on the same scene: one 64-lane
+// wave per env, lanes 0..23 build the env's body primitives into LDS, the rays are lane-strided.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +52,17 @@ struct Params {
     int32_t W, H, m;
     uint32_t flags;
     float mradius;
+    const int32_t* terrain_kind;  // [N] or null: the plane everywhere
+    float sn, cs, step_h, step_l;  // the slope's sine and cosine, the steps' height and length
+};
+
+// the ray-cast sensor's own arguments (the scene is a Params)
+struct RayParams {
+    const hr_ray* rays;  // [R], in the frame of `body`
+    float* dist;         // [N,R] or null
+    int32_t* hit;        // [N,R] or null
+    int32_t R, body, mode;
+    float max_range;
 };
 
 struct f3 {
@@ -177,6 +193,109 @@ __device__ inline bool intersect(const Prim& p, f3 o, f3 d, float& t, f3& n) {
     return true;
 }
 
+// ground: the plane z = 0
+__device__ inline bool hit_plane(f3 o, f3 d, float& t) {
+    if (!(d.z < 0.f && o.z > 0.f)) return false;
+    t = -o.z / d.z;
+    return true;
+}
+
+// The box steps along +x: cell c(x) = max(floor(x / L), 0) of height S c. The walk over the cells is
+// the header's, HR_MAX_STEP_CELLS cells at most. Two kinds of ray leave before it because no step of
+// it can give them a hit: one that does not descend and does not move up the stairs (treads need
+// d.z < 0, risers d.x > 0), and, inside the walk, a ray that does not descend once it has cleared a
+// riser while climbing faster than the stairs do (every later riser is cleared by more).
+// The walk does not begin at the ray's own cell when the ray starts well above the line z = S x / L
+// (from x < 0: the line through (o.x, 0) of that slope), which no tread or riser on the ray's way
+// reaches: the cells it crosses while it is more than m above that
+// line cannot give a hit, so the walk lands one cell before the first that might (they count towards
+// the HR_MAX_STEP_CELLS all the same, and t0 is the boundary's, as the walk would have left it). m is
+// 1e-4 of the heights involved, a thousand times the rounding of the walk's own z_b.
+// ckx: the x the steps' checker takes (a riser's is the middle of the tread below it).
+__device__ inline bool hit_steps(float L, float S, f3 o, f3 d, float farp, float& t, f3& n, float& ckx) {
+    float c = fmaxf(floorf(o.x / L), 0.f);
+    if (o.z <= S * c) return false;  // inside the solid: entry hits only
+    if (d.z >= 0.f && d.x <= 0.f) return false;
+    const bool outruns = d.z >= 0.f && d.z * L >= 1.01f * S * d.x;
+    float t0 = 0.f;
+    int it = 0;
+    {
+        const float k = S / L, xo = fmaxf(o.x, 0.f);
+        const float g0 = o.z - k * xo, g1 = d.z - k * d.x;  // height over the line, and its rate
+        const float m = 1e-4f * (fabsf(o.z) + k * xo + (float)HR_MAX_STEP_CELLS * S);
+        if (g0 > m && d.x > 0.f) {
+            if (g1 >= 0.f) return false;  // never comes down to it
+            const float cs = floorf((o.x + ((g0 - m) / -g1) * d.x) / L) - 1.f;
+            if (cs > c) {
+                if (cs - c >= (float)HR_MAX_STEP_CELLS) return false;
+                it = (int)(cs - c);
+                c = cs;
+                t0 = (c * L - o.x) / d.x;
+                if (t0 > farp) return false;
+            }
+        } else if (g0 > m && d.x < 0.f) {  // down the stairs, as far as cell 1 (cell 0 is all of x < L)
+            const float xs = g1 < 0.f ? o.x + ((g0 - m) / -g1) * d.x : -INFINITY;
+            const float cs = fmaxf(floorf(xs / L) + 1.f, 1.f);
+            if (cs < c) {
+                if (c - cs >= (float)HR_MAX_STEP_CELLS) return false;
+                it = (int)(c - cs);
+                t0 = ((cs + 1.f) * L - o.x) / d.x;
+                c = cs;
+                if (t0 > farp) return false;
+            }
+        }
+    }
+    for (; it < HR_MAX_STEP_CELLS; ++it) {
+        if (d.z < 0.f) {  // the tread
+            const float tt = (S * c - o.z) / d.z;
+            const float xt = o.x + tt * d.x;
+            if (tt >= t0 && xt < (c + 1.f) * L && (c == 0.f || xt >= c * L)) {
+                t = tt;
+                n = f3{0.f, 0.f, 1.f};
+                ckx = xt;
+                return true;
+            }
+        }
+        if (d.x > 0.f) {  // up the stairs: the riser of the next cell
+            const float tb = ((c + 1.f) * L - o.x) / d.x;
+            if (tb > farp) return false;
+            const float zb = o.z + tb * d.z, hn = S * (c + 1.f);
+            if (zb < hn) {
+                t = tb;
+                n = f3{-1.f, 0.f, 0.f};
+                ckx = (c + 0.5f) * L;
+                return true;
+            }
+            if (outruns && zb - hn >= 1e-4f * fabsf(zb)) return false;
+            c += 1.f;
+            t0 = tb;
+        } else if (d.x < 0.f) {  // down the stairs: a riser faces -x and is never entered from above
+            if (c == 0.f) return false;
+            const float tb = (c * L - o.x) / d.x;
+            if (tb > farp) return false;
+            c -= 1.f;
+            t0 = tb;
+        } else {
+            return false;
+        }
+    }
+    return false;
+}
+
+// entry hit of the env's terrain (kind 1 the slope, 2 the steps, anything else the plane)
+__device__ inline bool hit_terrain(const Params& P, int kind, f3 o, f3 d, float farp, float& t, f3& n, float& ckx) {
+    if (kind == 1) {
+        n = f3{-P.sn, 0.f, P.cs};
+        const float dn = dot(d, n), on = dot(o, n);
+        if (!(dn < 0.f && on > 0.f)) return false;
+        t = -on / dn;
+        return true;
+    }
+    if (kind == 2) return hit_steps(P.step_l, P.step_h, o, d, farp, t, n, ckx);
+    n = f3{0.f, 0.f, 1.f};
+    return hit_plane(o, d, t);
+}
+
 // may the ray touch the primitive's bounding sphere? Conservative: the slack covers the rounding of
 // the test itself (|q| carries about 4e-7 |m|), so culling never changes a pixel.
 __device__ inline bool may_hit(const Prim& p, f3 o, f3 d) {
@@ -273,6 +392,9 @@ __device__ inline uint32_t channel(float c) {
     return (uint32_t)(int)(c * 255.f + 0.5f);
 }
 
+// TERRAIN = false is the kernel of a renderer without a kind array: the ground is the plane at compile
+// time, and nothing of the terrain is in its code.
+template <bool TERRAIN>
 __global__ __launch_bounds__(256) void render_kernel(const Params P) {
     __shared__ Prim prims[kMaxPrims];
     __shared__ Cam cam;
@@ -280,6 +402,7 @@ __global__ __launch_bounds__(256) void render_kernel(const Params P) {
     const int k = blockIdx.z;
     const DCam& dc = P.cams[k];
     const int env = dc.env;
+    const int tk = TERRAIN ? P.terrain_kind[env] : 0;  // wave-uniform: a scalar load
     const int nprim = NB + P.m;
     if (tid < nprim) build_prim(P, env, tid, prims[tid]);
     if (tid == kMaxPrims) build_camera(P, dc, cam);
@@ -303,11 +426,20 @@ __global__ __launch_bounds__(256) void render_kernel(const Params P) {
     }
 
     float best = INFINITY;
-    int who = -2;  // -2 sky, -1 ground, else the primitive
+    int who = -2;  // -2 sky, -1 ground (the env's terrain), else the primitive
     f3 n{0.f, 0.f, 1.f};
-    if (d.z < 0.f && o.z > 0.f) {
-        const float t = -o.z / d.z;
-        if (t >= nearp && t <= farp) {
+    float ckx = 0.f;
+    if constexpr (TERRAIN) {
+        float t;
+        f3 nn;
+        if (hit_terrain(P, tk, o, d, farp, t, nn, ckx) && t >= nearp && t <= farp) {
+            best = t;
+            who = -1;
+            n = nn;
+        }
+    } else {
+        float t;
+        if (hit_plane(o, d, t) && t >= nearp && t <= farp) {
             best = t;
             who = -1;
         }
@@ -351,7 +483,7 @@ __global__ __launch_bounds__(256) void render_kernel(const Params P) {
     if (hit) {
         float ar, ag, ab;
         if (who < 0) {
-            const int par = (int)floorf(hp.x) + (int)floorf(hp.y);
+            const int par = (int)floorf(tk == 2 ? ckx : hp.x) + (int)floorf(hp.y);
             ar = ag = ab = ((P.flags & HR_FLAG_CHECKER) && (par & 1)) ? HR_GROUND_ODD : HR_GROUND_EVEN;
         } else {
             ar = prims[who].rgb[0], ag = prims[who].rgb[1], ab = prims[who].rgb[2];
@@ -365,6 +497,54 @@ __global__ __launch_bounds__(256) void render_kernel(const Params P) {
         if (P.color) P.color[px] = channel(cr) | channel(cg) << 8 | channel(cb) << 16 | 0xff000000u;
         if (P.depth) P.depth[px] = hit ? -best * dot(d, f) : -INFINITY;
         if (P.seg) P.seg[px] = sid;
+    }
+}
+
+// The ray-cast sensor: block = env, one wave. The hits are the image's with near = 0, far = max_range:
+// terrain first, then bodies 0..23, a strictly nearer one replaces; markers are never hit.
+__global__ __launch_bounds__(64) void rays_kernel(const Params P, const RayParams A) {
+    __shared__ Prim prims[NB];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    const int tk = P.terrain_kind ? P.terrain_kind[env] : 0;
+    const bool bodies = !(P.flags & HR_RAYS_SKIP_BODIES);
+    if (bodies && lane < NB) build_prim(P, env, lane, prims[lane]);
+    __syncthreads();
+    const float* row = P.rb + ((size_t)env * NB + A.body) * 13;
+    const f3 p = ld3(row);
+    const float* q = row + 3;
+    float hc = 1.f, hs = 0.f;  // the heading
+    if (A.mode == HR_RAY_FRAME_HEADING) {
+        const f3 hx = rot(q, f3{1.f, 0.f, 0.f});
+        const float l = sqrtf(hx.x * hx.x + hx.y * hx.y);
+        if (!(l < 1e-6f)) hc = hx.x / l, hs = hx.y / l;
+    }
+    for (int r = lane; r < A.R; r += 64) {
+        f3 ro = ld3(A.rays[r].origin), d = ld3(A.rays[r].dir);
+        if (A.mode == HR_RAY_FRAME_HEADING) {
+            ro = f3{hc * ro.x - hs * ro.y, hs * ro.x + hc * ro.y, ro.z};
+            d = f3{hc * d.x - hs * d.y, hs * d.x + hc * d.y, d.z};
+        } else if (A.mode == HR_RAY_FRAME_TRANSFORM) {
+            ro = rot(q, ro);
+            d = rot(q, d);
+        }
+        const f3 o = p + ro;
+        float best = INFINITY, t, ckx;
+        int who = -2;
+        f3 nn;
+        if (hit_terrain(P, tk, o, d, A.max_range, t, nn, ckx) && t >= 0.f && t <= A.max_range) {
+            best = t;
+            who = -1;
+        }
+        if (bodies) {
+            for (int b = 0; b < NB; ++b)
+                if (intersect(prims[b], o, d, t, nn) && t >= 0.f && t <= A.max_range && t < best) {
+                    best = t;
+                    who = b;
+                }
+        }
+        const size_t at = (size_t)env * A.R + r;
+        if (A.dist) A.dist[at] = best;
+        if (A.hit) A.hit[at] = who;
     }
 }
 
@@ -384,7 +564,34 @@ struct hr_renderer {
     const float* mpos = nullptr;
     int m = 0;
     float mradius = 0.f;
+    // hr_set_terrain: the borrowed kind array and the host's floats
+    const int32_t* terrain_kind = nullptr;
+    float sn = 0.f, cs = 1.f, step_h = 0.f, step_l = 1.f;
+    // hr_set_rays
+    DeviceArray<hr_ray> d_rays;
+    int ray_cap = 0;
+    int R = 0, ray_body = 0, ray_mode = 0;
 };
+
+namespace {
+
+// the scene both kernels read
+Params scene_params(const hr_renderer* h, const float* rb_state, uint32_t flags) {
+    Params P{};
+    P.rb = rb_state;
+    P.geom = h->d_geom;
+    P.body_rgb = h->body_rgb;
+    P.body_seg = h->body_seg;
+    P.flags = flags;
+    P.terrain_kind = h->terrain_kind;
+    P.sn = h->sn;
+    P.cs = h->cs;
+    P.step_h = h->step_h;
+    P.step_l = h->step_l;
+    return P;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -491,6 +698,72 @@ int hr_set_markers(hr_renderer* h, const float* pos, int m, const float* host_rg
     return 0;
 }
 
+int hr_set_terrain(hr_renderer* h, const int32_t* terrain_kind, float slope, float step_height, float step_length) {
+    if (!h) return fail("hr_set_terrain: null handle");
+    if (!std::isfinite(slope)) return fail("hr_set_terrain: slope %g is not finite", slope);
+    if (!(std::isfinite(step_height) && step_height >= 0.f)) return fail("hr_set_terrain: step_height %g is not finite and >= 0", step_height);
+    if (!(std::isfinite(step_length) && step_length > 0.f)) return fail("hr_set_terrain: step_length %g is not finite and > 0", step_length);
+    h->terrain_kind = terrain_kind;
+    h->sn = sinf(slope);
+    h->cs = cosf(slope);
+    h->step_h = step_height;
+    h->step_l = step_length;
+    return 0;
+}
+
+int hr_set_rays(hr_renderer* h, const hr_ray* rays, int R, int body, int frame_mode) {
+    if (!h) return fail("hr_set_rays: null handle");
+    if (!rays) return fail("hr_set_rays: null ray array");
+    if (R < 1 || R > HR_MAX_RAYS) return fail("hr_set_rays: %d rays, 1..%d", R, HR_MAX_RAYS);
+    if (body < 0 || body >= NB) return fail("hr_set_rays: body %d outside [0, %d)", body, NB);
+    if (frame_mode < HR_RAY_FRAME_POSITION || frame_mode > HR_RAY_FRAME_TRANSFORM)
+        return fail("hr_set_rays: frame_mode %d is not 0 (position), 1 (heading) or 2 (transform)", frame_mode);
+    for (int i = 0; i < R; ++i) {
+        double dd = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(rays[i].origin[a]) || !std::isfinite(rays[i].dir[a]))
+                return fail("hr_set_rays: ray %d has a component that is not finite", i);
+            dd += (double)rays[i].dir[a] * (double)rays[i].dir[a];
+        }
+        if (!(fabs(sqrt(dd) - 1.0) <= 1e-3)) return fail("hr_set_rays: ray %d: |dir| = %g is not of unit length", i, sqrt(dd));
+    }
+    HE_CHECK(hipSetDevice(h->device));
+    if (R > h->ray_cap) {
+        DeviceArray<hr_ray> p;
+        HE_CHECK(p.assign(rays, R));
+        h->d_rays = std::move(p);
+        h->ray_cap = R;
+    } else {
+        HE_CHECK(h->d_rays.upload(rays, R));
+    }
+    h->R = R;
+    h->ray_body = body;
+    h->ray_mode = frame_mode;
+    return 0;
+}
+
+int hr_cast_rays(hr_renderer* h, const float* rb_state, float max_range, float* dist_out, int32_t* hit_out, uint32_t flags,
+                 void* stream) {
+    if (!h) return fail("hr_cast_rays: null handle");
+    if (!rb_state) return fail("hr_cast_rays: null rb_state");
+    if (!dist_out && !hit_out) return fail("hr_cast_rays: no output buffer");
+    if (flags & ~HR_RAYS_SKIP_BODIES) return fail("hr_cast_rays: unknown flag bits 0x%x", flags & ~HR_RAYS_SKIP_BODIES);
+    if (!(std::isfinite(max_range) && max_range > 0.f)) return fail("hr_cast_rays: max_range %g is not finite and > 0", max_range);
+    if (h->R < 1) return fail("hr_cast_rays: no rays set (hr_set_rays)");
+    const Params P = scene_params(h, rb_state, flags);
+    RayParams A{};
+    A.rays = h->d_rays;
+    A.dist = dist_out;
+    A.hit = hit_out;
+    A.R = h->R;
+    A.body = h->ray_body;
+    A.mode = h->ray_mode;
+    A.max_range = max_range;
+    hipLaunchKernelGGL(rays_kernel, dim3(h->num_envs), dim3(64), 0, static_cast<hipStream_t>(stream), P, A);
+    HE_CHECK(hipGetLastError());
+    return 0;
+}
+
 int hr_render(hr_renderer* h, const float* rb_state, uint8_t* color, float* depth, int32_t* seg, uint32_t flags,
               void* stream) {
     if (!h) return fail("hr_render: null handle");
@@ -498,12 +771,8 @@ int hr_render(hr_renderer* h, const float* rb_state, uint8_t* color, float* dept
     if (!rb_state) return fail("hr_render: null rb_state");
     if (!color && !depth && !seg) return fail("hr_render: no output buffer");
     if (reinterpret_cast<uintptr_t>(color) & 3u) return fail("hr_render: the colour buffer must be 4-byte aligned");
-    Params P{};
-    P.rb = rb_state;
-    P.geom = h->d_geom;
+    Params P = scene_params(h, rb_state, flags);
     P.cams = h->d_cams;
-    P.body_rgb = h->body_rgb;
-    P.body_seg = h->body_seg;
     P.mpos = h->mpos;
     P.mrgb = h->d_mrgb;
     P.color = reinterpret_cast<uint32_t*>(color);
@@ -512,11 +781,11 @@ int hr_render(hr_renderer* h, const float* rb_state, uint8_t* color, float* dept
     P.W = h->W;
     P.H = h->H;
     P.m = h->m;
-    P.flags = flags;
     P.mradius = h->mradius;
     const dim3 grid((h->W + kTile - 1) / kTile, (h->H + kTile - 1) / kTile, h->k);
     if (grid.y > 65535u) return fail("hr_render: image height %d too large for one launch", h->H);
-    hipLaunchKernelGGL(render_kernel, grid, dim3(kTile, kTile, 1), 0, static_cast<hipStream_t>(stream), P);
+    hipLaunchKernelGGL(h->terrain_kind ? render_kernel<true> : render_kernel<false>, grid, dim3(kTile, kTile, 1), 0,
+                       static_cast<hipStream_t>(stream), P);
     HE_CHECK(hipGetLastError());
     return 0;
 }

@@ -481,6 +481,7 @@ class HumanoidPHC:
         n = self.cfg.num_envs
         self._viewed = None
         self._renderer = R.Renderer(self.engine)
+        self._renderer.set_terrain_from_engine()
         pal = torch.tensor(self.PALETTE, dtype=torch.float32, device=self.device)
         self._body_rgb = pal[torch.arange(n, device=self.device) % len(self.PALETTE)][:, None, :].expand(
             n, self.num_bodies, 3).contiguous()

@@ -721,6 +721,7 @@ class Gym:
             raise RuntimeError("render_all_camera_sensors without a camera sensor")
         if sim.renderer is None:
             sim.renderer = R.Renderer(sim.engine)
+        sim.renderer.set_terrain_from_engine()  # host values only: the engine's terrain as it is now
         if sim.cameras_dirty:
             sim.renderer.set_cameras([
                 R.camera(c.env, c.props.width, c.props.height, c.pos, c.target, hfov_deg=c.props.horizontal_fov,
@@ -747,6 +748,38 @@ class Gym:
         self._sync_renderer(sim)
         sim.renderer.render()
         sim.rendered = True
+        return True
+
+    # -- ray-cast sensor (engine extensions) ------------------------------------------------------------
+    def _ray_renderer(self, sim: Sim, what: str):
+        from .. import render as R
+        if sim.engine is None:
+            raise RuntimeError(f"{what} before prepare_sim")
+        self._flush(sim)  # the sensor sees the state after every simulate call so far
+        if sim.renderer is None:
+            sim.renderer = R.Renderer(sim.engine)
+        sim.renderer.set_terrain_from_engine()
+        return sim.renderer
+
+    def set_ray_sensor(self, sim: Sim, rays, body="Pelvis", frame="heading"):
+        """Engine extension: the rays of ``cast_ray_sensor``, [R,6] host values (origin 3, direction 3), the
+        same for every env, in a frame attached to ``body`` (an index or a name): "position", "heading" (about
+        z by the body's heading) or "transform". 1 to 1024 rays; they replace the rays set before.
+        ``humanoid_amd.render.height_scan_rays`` gives a grid of straight-down rays."""
+        self._ray_renderer(sim, "set_ray_sensor").set_rays(rays, body, frame)
+        return True
+
+    def cast_ray_sensor(self, sim: Sim, dist_desc, hit_desc, max_range, skip_bodies=True):
+        """Engine extension: one launch casts every env's rays at the current state against the env's terrain
+        and, unless ``skip_bodies``, its 24 body geoms. dist [N,R] f32: the distance along the ray, +inf where
+        nothing is hit within ``max_range``; hit [N,R] i32: -2 nothing, -1 terrain, else the body index. Either
+        descriptor may be None, not both."""
+        ren = self._ray_renderer(sim, "cast_ray_sensor")
+        if dist_desc is None and hit_desc is None:
+            from ..render import RenderError
+            raise RenderError("cast_ray_sensor: no output tensor")
+        ren.cast_rays(max_range, skip_bodies, None if dist_desc is None else self._tensor(dist_desc),
+                      None if hit_desc is None else self._tensor(hit_desc))
         return True
 
     def _image(self, sim: Sim, env: _Env, handle, image_type):

@@ -1,9 +1,10 @@
 """Headless camera sensors: ctypes shim over ``libhumanoid_render.so`` (``include/humanoid_render.h``).
 
 One HIP ray-casting kernel draws the engine's analytic scene (24 sphere / capsule / box geoms per
-env, marker spheres, the ground plane) straight from the engine's rigid-body state buffer; the
-library only reads the engine's memory. :class:`Renderer` owns the output images and launches on
-the engine's current stream. There is no CPU path and no window: without the library or a GPU
+env, marker spheres, the env's terrain: plane, slope or steps) straight from the engine's rigid-body
+state buffer; the library only reads the engine's memory. :class:`Renderer` owns the output images and
+launches on the engine's current stream. The same scene answers a ray-cast sensor (``set_rays`` /
+``cast_rays``: height scans, range fans), one launch for all envs. There is no CPU path and no window: without the library or a GPU
 the constructor raises.
 """
 from __future__ import annotations
@@ -27,6 +28,12 @@ SEG_MARKER = 1000
 MAX_MARKERS = 24
 FOLLOW_POSITION, FOLLOW_TRANSFORM, FOLLOW_POSITION_XY = 0, 1, 2
 BODY_RGB = (0.80, 0.68, 0.52)
+MAX_STEP_CELLS = 512
+MAX_RAYS = 1024
+RAY_FRAME_POSITION, RAY_FRAME_HEADING, RAY_FRAME_TRANSFORM = 0, 1, 2
+RAY_FRAMES = {"position": RAY_FRAME_POSITION, "heading": RAY_FRAME_HEADING, "transform": RAY_FRAME_TRANSFORM}
+RAYS_SKIP_BODIES = 1
+HIT_NOTHING, HIT_TERRAIN = -2, -1
 
 _V, _I = C.c_void_p, C.c_int
 # every exported symbol with its prototype (_abi.bind_library)
@@ -34,6 +41,8 @@ HR_PROTOTYPES = {
     "hr_last_error": (C.c_char_p, []), "hr_version": [], "hr_create": [_I, _V, _I, _V], "hr_destroy": [_V],
     "hr_validate_cameras": [_V, _I, _I], "hr_set_cameras": [_V, _V, _I], "hr_set_appearance": [_V, _V, _V],
     "hr_set_markers": [_V, _V, _I, _V, C.c_float], "hr_render": [_V, _V, _V, _V, _V, C.c_uint32, _V],
+    "hr_set_terrain": [_V, _V, C.c_float, C.c_float, C.c_float], "hr_set_rays": [_V, _V, _I, _I, _I],
+    "hr_cast_rays": [_V, _V, C.c_float, _V, _V, C.c_uint32, _V],
 }
 HR_SYMBOLS = tuple(HR_PROTOTYPES)
 
@@ -47,6 +56,23 @@ class HrCamera(C.Structure):
     _fields_ = [("env", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("hfov_deg", C.c_float),
                 ("near", C.c_float), ("far", C.c_float), ("follow_body", C.c_int32), ("follow_mode", C.c_int32),
                 ("pos", C.c_float * 3), ("target", C.c_float * 3)]
+
+
+class HrRay(C.Structure):
+    """include/humanoid_render.h hr_ray."""
+    _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+def height_scan_rays(nx: int, ny: int, spacing: float, height: float, offset=(0.0, 0.0)) -> np.ndarray:
+    """[nx*ny, 6] (origin, direction) of a grid of straight-down rays, ``spacing`` apart and centred on
+    ``offset`` in x and y, starting ``height`` above the body origin: with ``cast_rays`` the ground's height
+    under ray i is (body z + height) - dist[i]."""
+    x = (np.arange(int(nx)) - (int(nx) - 1) / 2) * float(spacing) + float(offset[0])
+    y = (np.arange(int(ny)) - (int(ny) - 1) / 2) * float(spacing) + float(offset[1])
+    rays = np.zeros((len(x), len(y), 6))
+    rays[..., 0], rays[..., 1], rays[..., 2] = x[:, None], y[None, :], float(height)
+    rays[..., 5] = -1.0
+    return rays.reshape(-1, 6)
 
 
 def camera(env: int, width: int, height: int, pos, target, hfov_deg: float = 90.0, near: float = 0.001,
@@ -96,6 +122,9 @@ class Renderer:
         self.color = self.depth = self.seg = None
         self._appearance = (None, None)
         self._markers = None
+        self._terrain = None
+        self.num_rays = 0
+        self.ray_dist = self.ray_hit = None
 
     def __del__(self):
         _abi.destroy_handle(self, "hr_destroy")
@@ -141,6 +170,72 @@ class Renderer:
         c = np.ascontiguousarray(np.broadcast_to(np.asarray(rgb, np.float32), (m, 3)))
         _check(self.lib.hr_set_markers(self.h, p, m, c.ctypes.data_as(C.c_void_p), float(radius)))
         self._markers = pos  # keep alive while attached
+
+    def set_terrain(self, kind=None, slope: float = 0.0, step_height: float = 0.0, step_length: float = 1.0):
+        """The ground of each env: ``kind`` i32 [N] (device tensor, read at render time: 1 the slope, 2 the
+        steps, anything else the plane) or ``None`` for the plane everywhere; ``slope`` in radians, the steps'
+        height and length in metres. A refused call raises and leaves the previous setting."""
+        import torch
+        p = None if kind is None else self._dev(kind, torch.int32, (self.num_envs,), "terrain kind")
+        _check(self.lib.hr_set_terrain(self.h, p, float(slope), float(step_height), float(step_length)))
+        self._terrain = kind  # keep alive while attached
+
+    def set_terrain_from_engine(self):
+        """The engine's own terrain: its sim params' slope and steps and the ``terrain_kind`` last given to
+        ``Engine.set_env_properties`` (none given: the plane)."""
+        par = self.engine.params
+        kind = getattr(self.engine, "_env_props", (None, None, None))[2]
+        self.set_terrain(kind, par.terrain_slope, par.step_height, par.step_length)
+
+    def set_rays(self, rays, body="Pelvis", frame="heading"):
+        """The ray-cast sensor's rays, [R,6] host values (origin 3, direction 3) in a frame attached to
+        ``body`` (an index or a name) of every env; ``frame``: "position" (world axes), "heading" (rotated
+        about z by the body's heading) or "transform" (the body's rotation). Directions are normalised in
+        float64 before they are rounded. (Re)allocates ``ray_dist`` f32 [N,R] and ``ray_hit`` i32 [N,R]."""
+        import torch
+        a = np.array(rays, np.float64)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise RenderError(f"rays must be [R, 6] (origin, direction), got {a.shape}")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a[:, 3:] /= np.linalg.norm(a[:, 3:], axis=1, keepdims=True)
+        if isinstance(body, str):
+            from .body_sets import BODY_NAMES
+            if body not in BODY_NAMES:
+                raise RenderError(f"set_rays: no body named {body!r}")
+            body = BODY_NAMES.index(body)
+        if isinstance(frame, str):
+            if frame not in RAY_FRAMES:
+                raise RenderError(f"set_rays: unknown frame {frame!r} (one of {sorted(RAY_FRAMES)})")
+            frame = RAY_FRAMES[frame]
+        r = int(a.shape[0])
+        arr = (HrRay * max(r, 1))()
+        np.frombuffer(arr, np.float32)[:r * 6] = a.astype(np.float32).reshape(-1)
+        _check(self.lib.hr_set_rays(self.h, arr, r, int(body), int(frame)))
+        if r != self.num_rays:
+            self.ray_dist = torch.zeros(self.num_envs, r, dtype=torch.float32, device=self.device)
+            self.ray_hit = torch.zeros(self.num_envs, r, dtype=torch.int32, device=self.device)
+            self.num_rays = r
+
+    def cast_rays(self, max_range: float, skip_bodies: bool = True, dist=None, hit=None, rb_state=None):
+        """hr_cast_rays: one launch for all envs, no host synchronisation. Returns (dist f32 [N,R]: t, +inf
+        where nothing is hit within ``max_range``; hit i32 [N,R]: HIT_NOTHING, HIT_TERRAIN or the body
+        index). With neither ``dist`` nor ``hit`` given the renderer's own ``ray_dist`` / ``ray_hit`` are
+        filled; given one of them only that is written. ``skip_bodies``: the terrain only. Every tensor is
+        checked to be on the device, contiguous, of its dtype and at least N*R long before a pointer is
+        passed."""
+        import torch
+        if self.num_rays < 1:
+            raise RenderError("cast_rays before set_rays")
+        if dist is None and hit is None:
+            dist, hit = self.ray_dist, self.ray_hit
+        n = self.num_envs * self.num_rays
+        p_dist = None if dist is None else self._dev(dist, torch.float32, None, "dist", n)
+        p_hit = None if hit is None else self._dev(hit, torch.int32, None, "hit", n)
+        p_rb = self._dev(self.engine.rb_state if rb_state is None else rb_state, torch.float32, None, "rb_state",
+                         self.num_envs * _abi.NB * 13)
+        _check(self.lib.hr_cast_rays(self.h, p_rb, float(max_range), p_dist, p_hit,
+                                     RAYS_SKIP_BODIES if skip_bodies else 0, self.engine.stream))
+        return dist, hit
 
     def render_into(self, color=None, depth=None, seg=None, flags: int = FLAGS_DEFAULT, rb_state=None):
         """hr_render into caller tensors (``None``: that output is not written). ``rb_state`` defaults to

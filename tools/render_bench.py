@@ -7,7 +7,15 @@ Next to each time the record carries the plain work count of a launch without cu
 primitives tested by the primary rays (48 per pixel: 24 geoms + 24 markers) and, with shadows, 24 more for
 every pixel that hits something lit -- so the figure can be judged.
 
-    python tools/render_bench.py [--out profiles/r08/render_bench.json]
+Two more groups of cases follow the plane's (--cases picks: plane, terrain, rays, or all): the same two camera
+sets with every env on the box steps (hr_set_terrain, shadows and culling on; the sky rays walk the cells of
+the steps, so the frame costs more than the plane's), and the ray-cast sensor (hr_cast_rays) as a height scan
+of 11 x 11 rays under each of 4096 standing humanoids, terrain only and with the bodies.
+
+--lib times another build of the render library at the same shapes (the parent commit's, say, next to this
+one's, alternately, in processes of their own); cases whose entry points that build lacks are left out.
+
+    python tools/render_bench.py [--out profiles/r08/render_bench.json] [--cases all] [--lib PATH]
 """
 import argparse
 import json
@@ -33,17 +41,40 @@ def standing_pose(model, n, rng):
     return rb
 
 
+def timed(fn, warmup, launches):
+    """ms per call: HIP events around `launches` calls after `warmup` calls."""
+    import torch
+    for _ in range(warmup):
+        fn()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(launches):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / launches
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "render_bench.json"))
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--launches", type=int, default=100)
+    ap.add_argument("--cases", default="all", choices=("all", "plane", "terrain", "rays"))
+    ap.add_argument("--lib", default=None, help="another build of libhumanoid_render.so to time")
     args = ap.parse_args()
     import torch
     from humanoid_amd import build
     from humanoid_amd import render as R
     from humanoid_amd.engine import Engine
     from humanoid_amd.model import load_default_model
+    if args.lib:  # bind what that build exports; a case that needs more is left out below
+        import ctypes
+        other = ctypes.CDLL(args.lib)
+        R._LIBRARY.prototypes = {k: v for k, v in R.HR_PROTOTYPES.items() if hasattr(other, k)}
+        R.load_library(args.lib)
+    has_new = "hr_set_terrain" in R._LIBRARY.prototypes
+    want = lambda group: args.cases in ("all", group) and (group == "plane" or has_new)  # noqa: E731
     model = load_default_model()
     n = 64
     eng = Engine(model, n, device=0)
@@ -63,25 +94,48 @@ def main():
         hit = int(torch.isfinite(ren.depth).sum())
         for shadows in (True, False):
             for cull in (True, False):
+                if not want("plane"):
+                    continue
                 flags = R.FLAG_CHECKER | (R.FLAG_SHADOWS if shadows else 0) | (0 if cull else R.FLAG_NO_CULL)
-                for _ in range(args.warmup):
-                    ren.render(flags)
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                for _ in range(args.launches):
-                    ren.render(flags)
-                t1.record()
-                torch.cuda.synchronize()
-                ms = t0.elapsed_time(t1) / args.launches
+                ms = timed(lambda: ren.render(flags), args.warmup, args.launches)
                 tests = pixels * 48 + (hit * 24 if shadows else 0)
                 results.append(dict(case=name, cameras=k, width=w, height=h, shadows=shadows, culling=cull,
                                     ms_per_render=round(ms, 5), pixels=pixels, pixels_hit=hit,
                                     primitive_tests_unculled=tests,
                                     gtests_per_s_unculled_equivalent=round(tests / ms / 1e6, 2)))
                 print(json.dumps(results[-1]), flush=True)
+        if want("terrain"):  # every env on the steps of the engine's defaults (0.05 m x 0.4 m)
+            par = eng.params
+            kind = torch.full((n,), 2, dtype=torch.int32, device=eng.device)
+            ren.set_terrain(kind, par.terrain_slope, par.step_height, par.step_length)
+            ren.render(R.FLAGS_DEFAULT)
+            torch.cuda.synchronize()
+            hit_t = int(torch.isfinite(ren.depth).sum())
+            ms = timed(lambda: ren.render(R.FLAGS_DEFAULT), args.warmup, args.launches)
+            results.append(dict(case=name + "-steps", cameras=k, width=w, height=h, shadows=True, culling=True,
+                                terrain="steps", step_height=par.step_height, step_length=par.step_length,
+                                ms_per_render=round(ms, 5), pixels=pixels, pixels_hit=hit_t))
+            print(json.dumps(results[-1]), flush=True)
+            ren.set_terrain(None)
+    if want("rays"):  # a height scan under each of 4096 standing humanoids, half of them on the steps
+        big, grid = 4096, 11
+        eng_r = Engine(model, big, device=0)
+        eng_r.rb_state.view(big, 24, 13).copy_(torch.from_numpy(standing_pose(model, big, rng)).to(eng_r.device))
+        scan = R.Renderer(eng_r)
+        kind = (torch.arange(big, device=eng_r.device) % 2 * 2).to(torch.int32)
+        scan.set_terrain(kind, eng_r.params.terrain_slope, eng_r.params.step_height, eng_r.params.step_length)
+        scan.set_rays(R.height_scan_rays(grid, grid, 0.1, 1.0), body="Pelvis", frame="heading")
+        for skip in (True, False):
+            ms = timed(lambda: scan.cast_rays(10.0, skip_bodies=skip), args.warmup, args.launches)
+            rays = big * grid * grid
+            results.append(dict(case=f"rays-{big}x{grid * grid}", envs=big, rays_per_env=grid * grid, skip_bodies=skip,
+                                ms_per_cast=round(ms, 5), grays_per_s=round(rays / ms / 1e6, 3),
+                                rays_hit=int(torch.isfinite(scan.ray_dist).sum())))
+            print(json.dumps(results[-1]), flush=True)
     rec = dict(tool="tools/render_bench.py", device=torch.cuda.get_device_name(0), warmup=args.warmup,
-               launches=args.launches, envs=n, primitives_per_env=48,
-               render_library_device_code_id=build.device_code_id(build.RENDER_LIB), results=results)
+               launches=args.launches, envs=n, primitives_per_env=48, cases=args.cases,
+               render_library=os.path.relpath(args.lib, ROOT) if args.lib else "humanoid_amd/libhumanoid_render.so",
+               render_library_device_code_id=build.device_code_id(args.lib or build.RENDER_LIB), results=results)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)
