@@ -313,7 +313,7 @@ HE_DEV int self_pairs(Lds& L, const GeomPrefetch& g, float off, int terr_all, in
         const int pre = wave_prefix(hit, lane, total);
         visit(hit, i, j, px, pn, pgap, terr_all + nhit + pre);
         nhit += total;
-        if (s0 + W < nsurv) compact(s0 + W);  // more than W survivors: the next pass (rare)
+        if (__builtin_expect(s0 + W < nsurv, 0)) compact(s0 + W);  // more than W survivors: the next pass (rare)
     }
     return nhit;
 }
@@ -424,7 +424,7 @@ HE_DEV int gen_contacts(Lds& L, const GeomPrefetch& g, const he_sim_params& p, i
         nc = nlim + terr_all + self_all < maxc ? nlim + terr_all + self_all : maxc;
     }
     const int ncand_all = nlim_all + terr_all + self_all;
-    if ((nlim + terr_all + self_all > maxc || nlim + rows_terr + 3 * self_all > MAXR) && nlim < maxc)
+    if (__builtin_expect((nlim + terr_all + self_all > maxc || nlim + rows_terr + 3 * self_all > MAXR) && nlim < maxc, 0))
         nc = reduce_overflow<TGS>(L, g, ter, off, self_col, lane, maxc, nlim, terr_all, self_all, tc, st);
     STAMP(PH_SELF_SLOTS);
     if (lane == 0) { L.nc = nc; L.nlim = nlim; L.ncand = ncand_all; }

@@ -421,7 +421,7 @@ HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, i
     float w0 = s.brow;
     if (__ballot(g0 != 0.f)) w0 += warm_residual(s.acol, g0, nrb);  // wave-uniform
     float lamv;
-    if (nrb <= 32) lamv = solve_tgs<32, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
+    if (__builtin_expect(nrb <= 32, 1)) lamv = solve_tgs<32, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
     else lamv = solve_tgs<MAXR, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
     L.lam[lane] = r.act ? lamv : 0.f;
     if (lane == 0) L.nwc = p.warm_start ? nr : 0;

@@ -66,10 +66,6 @@ HE_DEV float here(void) {
     return r;
 }
 HE_DEV void half_sincos(float x, float& sn, float& cs) {
-    if (__builtin_expect(x > 1.0f, 0)) {
-        sincosf(x, &sn, &cs);
-        return;
-    }
     const float x2 = x * x;
     float ps = fmaf(x2, 2.75573192e-6f, here<0xb9500d01u>());  // -1.98412698e-4
     ps = fmaf(x2, ps, 8.33333333e-3f);
@@ -80,6 +76,12 @@ HE_DEV void half_sincos(float x, float& sn, float& cs) {
     pc = fmaf(x2, pc, 4.16666667e-2f);
     pc = fmaf(x2, pc, -0.5f);
     cs = fmaf(x2, pc, 1.0f);
+    // the large-angle lanes, rare: tested once for the wave, so that the common case is one scalar branch
+    // not taken and ocml's argument reduction sits behind the hot stream (the series' value on such a
+    // lane is finite or inf and is replaced)
+    if (__builtin_expect(__ballot(x > 1.0f) != 0ull, 0)) {
+        if (x > 1.0f) sincosf(x, &sn, &cs);
+    }
 }
 HE_DEV float atan01(float t) {  // t in [0, 1]
     const float t2 = t * t;
@@ -94,21 +96,24 @@ HE_DEV float atan01(float t) {  // t in [0, 1]
 }
 HE_DEV f4 pqexp(f3 v) {
     const float th = __builtin_amdgcn_sqrtf(dot3(v, v));
-    if (th < 1e-8f) return qnormalize(f4{0.5f * v.x, 0.5f * v.y, 0.5f * v.z, 1.f});
     float sh, ch;
     half_sincos(0.5f * th, sh, ch);
     const float s = sh * __builtin_amdgcn_rcpf(th);
-    return f4{v.x * s, v.y * s, v.z * s, ch};
+    f4 r = f4{v.x * s, v.y * s, v.z * s, ch};
+    if (__ballot(th < 1e-8f) != 0ull) {
+        const f4 r0 = qnormalize(f4{0.5f * v.x, 0.5f * v.y, 0.5f * v.z, 1.f});
+        if (th < 1e-8f) r = r0;
+    }
+    return r;
 }
 HE_DEV f3 pqlog(f4 q) {
     if (q.w < 0.f) q = qneg(q);
     const float s = __builtin_amdgcn_sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
-    if (s < 1e-8f) return f3{2.f * q.x, 2.f * q.y, 2.f * q.z};
     // atan2(s, w) on the first quadrant (s > 0, w >= 0): the smaller over the larger, then pi / 2 - a
     const float lo = fminf(s, q.w), hi = fmaxf(s, q.w);
     const float a = atan01(lo * __builtin_amdgcn_rcpf(hi));
     const float ang = s > q.w ? 1.57079632679f - a : a;
-    const float k = 2.f * ang * __builtin_amdgcn_rcpf(s);
+    const float k = s < 1e-8f ? 2.f : 2.f * ang * __builtin_amdgcn_rcpf(s);  // the small-angle lanes: 2 q
     return f3{q.x * k, q.y * k, q.z * k};
 }
 

@@ -237,6 +237,9 @@ HE_DEV bool angle_row(f3 th, f3 u, const he_sim_params& p, float& gap, f3& dir) 
     return t >= 1e-6f && gap < p.limit_margin + p.dt * fmaxf(closing, 0.f);
 }
 
+// the scalar part of a joint rotation at limit_clamp's cap, cos((pi - kLimitGuard / 2) / 2): its first test,
+// which integrate_bodies makes once for the wave in front of the call
+constexpr float kWcap = 0.00499997917f;
 // Backstop when the limit rows lose (oracle/he_oracle_physics.c limit_clamp): a limit against a
 // deep self contact has no solution, and a joint near 100 rad/s can cross the margin in one
 // substep. nq = exp(q_old) (x) exp(dt w) before the log (exp(q_old) has w >= 0: the kinematics'
@@ -248,7 +251,6 @@ HE_DEV bool angle_row(f3 th, f3 u, const he_sim_params& p, float& gap, f3& dir) 
 HE_DEV bool limit_clamp(f4 nq, f3& nv, float (&w)[3]) {
     constexpr float kTwoPi = 6.28318530717959f;
     constexpr float cap = 3.14159265358979f - 0.5f * kLimitGuard;
-    constexpr float kWcap = 0.00499997917f;  // cos(cap / 2)
     if (nq.w >= kWcap) return false;         // inside the cap, not crossed: the common case
     const float t0 = sqrtf(dot3(nv, nv));
     if (!(t0 >= 1e-12f)) return false;
@@ -297,9 +299,13 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
     {
         // the joint's relative rate: PhysX articulation joint maxJointVelocity
         const float n2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];  // squared: the norm only where it acts
-        if (!root && n2 > p.max_joint_velocity * p.max_joint_velocity) {
-            const float s = p.max_joint_velocity / sqrtf(n2);
-            w[0] *= s; w[1] *= s; w[2] *= s;
+        // rare: one test for the wave (a lane >= NB carries body 1's rates)
+        const bool fast = n2 > p.max_joint_velocity * p.max_joint_velocity;
+        if (__builtin_expect((__ballot(fast) & ~1ull) != 0ull, 0)) {
+            if (!root && fast) {
+                const float s = p.max_joint_velocity / sqrtf(n2);
+                w[0] *= s; w[1] *= s; w[2] *= s;
+            }
         }
         // the link's WORLD angular velocity (asset max_angular_velocity, PxRigidBody): w_b = w_parent +
         // R_b u_b summed along the chain (Acc is scratch here), clamped link by link; the joint rates
@@ -309,8 +315,10 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
         // the clamp are then skipped (wave-uniform), with the result they would give
         const float un = __builtin_amdgcn_sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);  // a skip test with a 1 % margin
         const float wroot = regla::rdlane(un, 0);
-        const bool may = bl && !root && un * (float)(smpl::kNumBodyLevels - 1) > 0.99f * p.max_angular_velocity - wroot;
-        if (__ballot(may) != 0ull) {
+        // every lane compares (no short-circuit region); the joints' lanes picked from the ballot
+        const uint64_t may = __ballot(un * (float)(smpl::kNumBodyLevels - 1) > 0.99f * p.max_angular_velocity - wroot) &
+                             (((1ull << NB) - 1ull) & ~1ull);
+        if (__builtin_expect(may != 0ull, 0)) {
         const f4 qb = bl ? f4{L.qw[lane][0], L.qw[lane][1], L.qw[lane][2], L.qw[lane][3]} : f4{0.f, 0.f, 0.f, 1.f};
         const f3 wr = root ? f3{w[0], w[1], w[2]} : qapply(qb, f3{w[0], w[1], w[2]});
         // chain prefix by pointer jumping (the table stops below the root: its rate is added last)
@@ -334,7 +342,7 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
         const float wmax = p.max_angular_velocity;
         const float wn2 = dot3(wo, wo);
         const bool over = bl && wn2 > wmax * wmax;
-        if (__ballot(over) != 0ull) {  // rare (wave-uniform branch)
+        if (__builtin_expect(__ballot(over) != 0ull, 0)) {  // rare (wave-uniform branch)
             const f3 wc = over ? wo * (wmax * __builtin_amdgcn_rsqf(wn2)) : wo;
             const int pb = bl && !root ? T.chain[lane][T.depth[lane] - 1] : 0;
             const f3 wp = f3{__shfl(wc.x, pb, W), __shfl(wc.y, pb, W), __shfl(wc.z, pb, W)};
@@ -361,7 +369,8 @@ HE_DEV void integrate_bodies(Lds& L, const BodyTopo& T, int lane, const he_sim_p
         } else {
             f3 nv = pqlog(nq);
             f4 nql = nq;
-            if (p.joint_limits && limit_clamp(nq, nv, w)) {  // rare: the limit rows lost
+            // rare: the limit rows lost. limit_clamp's own first test, once for the wave's joints
+            if (p.joint_limits && __builtin_expect(__ballot(!(nq.w >= kWcap)) != 0ull, 0) && limit_clamp(nq, nv, w)) {
                 if (write_out) { L.u0[d0] = w[0]; L.u0[d0 + 1] = w[1]; L.u0[d0 + 2] = w[2]; }
                 nql = pqexp(nv);
             }
