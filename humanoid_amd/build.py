@@ -109,6 +109,10 @@ MIN_KERNELS = {"he_physics.hip": 2}
 NO_SCRATCH = {"hr_render.hip": ("render_kernelILb0", "render_kernelILb1", "rays_kernel"),
               "hd_dynamics.hip": "dynamics_kernel", "hs_solve.hip": ("solve_kernel", "torque_kernel"),
               "ht_task.hip": "task_kernel"}
+# further kernels of a source under the same rule, checked after NO_SCRATCH's: a second query family
+# compiled in a library's translation unit (hd_centroidal.h in hd_dynamics.hip: the lanes' columns in
+# registers, everything indexed in LDS)
+NO_SCRATCH_ALSO = {"hd_dynamics.hip": ("centroidal_kernel",)}
 # ceilings on the physics kernels' register spills, by exact kernel name: (scratch bytes per lane,
 # spilled VGPRs) of the compiler's resource report, no slack (as the occupancy). The TGS kernel's
 # spills are a plan, not a by-product: what is parked is the <= 32-row class's columns
@@ -148,7 +152,8 @@ def _check_scratch(src, stderr):
     if not names:
         return
     report = resource_report(stderr)
-    for name in (names,) if isinstance(names, str) else names:
+    names = ((names,) if isinstance(names, str) else tuple(names)) + NO_SCRATCH_ALSO.get(os.path.basename(src), ())
+    for name in names:
         scratch = [b["scratch"] for fn, b in report.items() if name in fn and b["scratch"] is not None]
         if not scratch:
             raise RuntimeError(f"{name}: no scratch size in the compiler's resource report")

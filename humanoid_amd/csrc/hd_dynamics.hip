@@ -246,3 +246,7 @@ int hd_compute(hd_dynamics* h, const float* root_state, const float* dof_state, 
 }
 
 }  // extern "C"
+
+// the centroidal queries (include/humanoid_centroidal.h, the hc_ entry points): a second kernel and entry-point
+// family of this library, kept in a header of their own and included last
+#include "hd_centroidal.h"

@@ -126,6 +126,16 @@ class Dynamics(_abi.QueryBinding):
         self._task.armature, self._task.gravity = self.armature, self.gravity
         return self._task
 
+    @property
+    def centroidal(self):
+        """The :class:`humanoid_amd.centroidal.Centroidal` of this engine (created on first use): centre of
+        mass, momentum, the centroidal momentum matrix and the energies. It has no settings to hand over:
+        armature and gravity do not enter its momentum rows."""
+        if getattr(self, "_centroidal", None) is None:
+            from .centroidal import Centroidal
+            self._centroidal = Centroidal(self.engine)
+        return self._centroidal
+
     def forward_dynamics(self, gen_force=None, out=None):
         """qdd [N,75] = M^-1 (gen_force - c) at the engine's current state: one launch, M never written."""
         return self.solver.forward_dynamics(gen_force, out)

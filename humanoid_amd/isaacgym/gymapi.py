@@ -46,7 +46,11 @@ Engine-specific behaviour (documented, not silent):
 * ENGINE EXTENSION: task-space control in one launch (``include/humanoid_task.h``): ``set_task_rows``
   names up to 32 task rows (velocity components of points on bodies, the same for every env), and
   ``solve_task_space`` gives the generalised force (``mode="force"``: ``J^T F``) or the joint torques
-  (``mode="joint"``, for ``set_dof_actuation_force_tensor``) that give those rows a desired acceleration.
+  (``mode="joint"``, for ``set_dof_actuation_force_tensor``) that give those rows a desired acceleration;
+* ENGINE EXTENSION: the balance quantities in one launch (``include/humanoid_centroidal.h``):
+  ``acquire_centroidal_tensor(sim, actor, which)`` for the centre of mass, its velocity, the momentum
+  about the centre of mass, the centroidal momentum matrix [N,6,75], its rate term and the energies, and
+  ``refresh_centroidal_tensors``, which refreshes every acquired one.
 """
 from __future__ import annotations
 
@@ -240,6 +244,7 @@ class Sim:
         self.dynamics = None          # humanoid_amd.dynamics.Dynamics, created by the first acquire
         self.dynamics_acquired = set()  # of "jacobian", "mass_matrix", "bias"
         self.task_stage = None        # [N,75] the (0_6; tau) solve_task_space's joint mode writes
+        self.centroidal_acquired = set()  # of humanoid_amd.centroidal.OUTPUTS
 
 
 # ----------------------------------------------------------------------------------- the Gym object
@@ -556,6 +561,35 @@ class Gym:
                                    want_qdd=qdd_out_desc is not None)
         if joint:
             out.copy_(u[:, 6:])
+        return True
+
+    # -- balance quantities (engine extensions) -----------------------------------------------------
+    def acquire_centroidal_tensor(self, sim: Sim, actor_name: str, which: str):
+        """Engine extension: one of the centroidal tensors (``include/humanoid_centroidal.h``), ``which`` in
+        "com" [N,3], "com_vel" [N,3], "momentum" [N,6] (linear, angular about the centre of mass), "cmm"
+        [N,6,75] (the centroidal momentum matrix), "cmm_bias" [N,6], "energy" [N,2] (kinetic, potential).
+        Filled by ``refresh_centroidal_tensors``."""
+        from ..centroidal import OUTPUTS
+        if sim.engine is None:
+            raise RuntimeError("acquire_centroidal_tensor before prepare_sim")
+        if not any(env.actor == actor_name for env in sim.envs):
+            raise ValueError(f"no env has an actor named {actor_name!r}")
+        if which not in OUTPUTS:
+            raise ValueError(f"acquire_centroidal_tensor: unknown tensor {which!r} (one of {OUTPUTS})")
+        if sim.dynamics is None:
+            from ..dynamics import Dynamics
+            sim.dynamics = Dynamics(sim.engine)
+        sim.centroidal_acquired.add(which)
+        t = getattr(sim.dynamics.centroidal, which)
+        return GymTensor(t.data_ptr(), t.shape, 1, sim.device, owner=t)
+
+    def refresh_centroidal_tensors(self, sim: Sim):
+        """Engine extension: every acquired centroidal tensor, in one launch, at the state after every
+        ``simulate`` call so far. Before any acquire: a no-op that reports success."""
+        if sim.centroidal_acquired:
+            from ..centroidal import OUTPUTS
+            self._flush(sim)
+            sim.dynamics.centroidal.refresh(**{name: name in sim.centroidal_acquired for name in OUTPUTS})
         return True
 
     def _flush(self, sim: Sim):

@@ -1,0 +1,406 @@
+"""CPU checks of the centroidal queries (include/humanoid_centroidal.h): the header, the hc_ symbols and
+refusals of libhumanoid_dynamics.so, the build's scratch rule, the binding's checks, the facade's guards,
+and the numpy reference of tests/centroidal_reference.py (the yardstick of tests/test_gpu_centroidal.py)
+against its pins: the header's identities, a finite difference of the momentum along the configuration
+flow, and the fp64 oracle. The kernel itself is checked on the GPU (test_gpu_centroidal.py).
+
+Measured here on the four seeded states, float64 (each bound below is 10 x its figure):
+
+    A_G qd - momentum, relative to max|momentum|                    4.9e-16
+    A_G - re-referenced base rows of M, relative to max|A_G|         7.0e-17
+    A_G[0:3,0:3] - m 1 and A_G[3:6,0:3], relative to m               4.7e-16
+    cmm_bias - central difference (h = 1e-5), relative to max|bias|  9.5e-10
+    cmm_bias - re-referenced no-gravity bias force, relative         1.6e-16
+    P, L_G, kinetic - oracle, relative                               1.2e-16, 8.7e-16, 1.1e-16
+    potential - oracle, relative (bound: 2^-24, a float32 g)         1.6e-16
+    kinetic - 1/2 qd^T M qd, relative                                2.3e-15
+
+and the float32 floors of the reference (the brackets below are a decade either side):
+
+    com 4.8e-07 m, com_vel 1.5e-07 m/s, momentum 5.7e-05, cmm / max|A_G| 5.0e-07, cmm_bias 1.3e-05,
+    kinetic 4.5e-06 J, potential 4.9e-04 J
+
+The refusals that a handle must get past its null check are sent with a stand-in handle, a zeroed block of
+memory: hc_compute checks its arguments before it reads the handle."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cases  # noqa: E402
+import centroidal_reference as CR  # noqa: E402
+import dynamics_reference as DR  # noqa: E402
+
+from humanoid_amd import _abi  # noqa: E402
+from humanoid_amd import centroidal as CM  # noqa: E402  (the binding under test: its outputs are the reference's)
+from oracle import oracle as O  # noqa: E402
+
+assert CM.OUTPUTS == CR.OUTPUTS
+
+HEADER = os.path.join(ROOT, "include", "humanoid_centroidal.h")
+NB, ND, NG = DR.NB, DR.ND, DR.NG
+
+
+def _lib():
+    from humanoid_amd import build, centroidal
+    if not os.path.exists(centroidal.LIB_PATH):
+        build.build()
+    return centroidal.load_library()
+
+
+# ------------------------------------------------------------------ header, symbols, build rules
+def test_header_compiles_as_c_and_the_struct_matches(tmp_path):
+    from humanoid_amd import centroidal
+    src = tmp_path / "hc.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "humanoid_centroidal.h"\n'
+                   'int main(void){printf("%d %d %d %d", HC_MOMENTUM_ROWS, HC_NUM_OUTPUTS, HE_NUM_GEN, (int)sizeof(hc_outputs));\n'
+                   'printf(" %d %d %d %d %d %d\\n", (int)offsetof(hc_outputs, com), (int)offsetof(hc_outputs, com_vel), '
+                   "(int)offsetof(hc_outputs, momentum), (int)offsetof(hc_outputs, cmm), (int)offsetof(hc_outputs, cmm_bias), "
+                   "(int)offsetof(hc_outputs, energy)); return 0;}\n")
+    exe = tmp_path / "hc"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
+                    "-o", str(exe)], check=True)
+    out = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    S = centroidal.HcOutputs
+    assert out == [centroidal.MOMENTUM_ROWS, len(centroidal.OUTPUTS), centroidal.NG, C.sizeof(S)] + \
+        [getattr(S, name).offset for name in centroidal.OUTPUTS]
+    assert centroidal.OUTPUTS == CR.OUTPUTS == tuple(name for name, _ in S._fields_)
+
+
+def test_library_exports_exactly_the_declared_symbols_of_both_families():
+    from humanoid_amd import centroidal, dynamics
+    lib = _lib()  # loads without a GPU
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    syms = sorted(set(re.findall(r"\b(hc_[a-z_0-9]+)\s*\(", text)))
+    assert len(syms) == 6
+    assert set(syms) == set(centroidal.HC_PROTOTYPES) == set(centroidal.HC_SYMBOLS)
+    assert not [s for s in syms if not hasattr(lib, s)]
+    assert lib.hc_version() == 1
+    # the other families' header scans must not pick anything up from this header
+    assert not re.findall(r"\bh[edrst]_[a-z_0-9]+\s*\(", text)
+    assert centroidal.LIB_PATH == dynamics.LIB_PATH
+    nm = subprocess.run(["nm", "-D", "--defined-only", centroidal.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in nm.splitlines() if ln.split()}
+    assert {s for s in exported if s.startswith("hc_")} == set(centroidal.HC_PROTOTYPES)
+    assert {s for s in exported if s.startswith("hd_")} == set(dynamics.HD_PROTOTYPES)
+    assert not [s for s in exported if re.match(r"h[erst]_", s)]
+
+
+def test_the_family_lives_in_the_dynamics_translation_unit():
+    from humanoid_amd import build
+    assert [s for s, _ in build.DYNAMICS_SOURCES] == ["hd_dynamics.hip"] and len(build.LIBRARIES) == 6
+    assert any(h.endswith("humanoid_centroidal.h") for h in build.HEADERS)
+    assert any(h.endswith("hd_centroidal.h") for h in build.HEADERS)
+    src = open(os.path.join(build.CSRC, "hd_dynamics.hip")).read()
+    assert src.rstrip().endswith('#include "hd_centroidal.h"')
+    assert not [f for f in os.listdir(build.CSRC) if f.startswith("hc_")]
+
+
+def test_scratch_check_names_the_centroidal_kernel():
+    from humanoid_amd import build
+
+    def report(**scratch):
+        return "\n".join(f"remark: Function Name: _ZN12_GLOBAL__N_1{len(k)}{k}E\nremark:     ScratchSize [bytes/lane]: {v}"
+                         for k, v in scratch.items())
+
+    assert build.NO_SCRATCH_ALSO["hd_dynamics.hip"] == ("centroidal_kernel",)
+    build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0, centroidal_kernel=0))
+    with pytest.raises(RuntimeError, match="centroidal_kernel: 8 bytes"):
+        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0, centroidal_kernel=8))
+    with pytest.raises(RuntimeError, match="centroidal_kernel: no scratch size"):
+        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0))
+    with pytest.raises(RuntimeError, match="dynamics_kernel: 4 bytes"):  # the dynamics kernel is checked first
+        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=4, centroidal_kernel=8))
+
+
+# ------------------------------------------------------------------ refusals, no GPU
+def test_refusals_come_with_their_reason_and_in_the_stated_order(he_model):
+    import copy
+    from humanoid_amd import centroidal
+    lib = _lib()
+    g = (C.c_float * 3)(0.0, 0.0, -9.81)
+    h = C.c_void_p()
+
+    def reason(rc):
+        assert rc != 0
+        return lib.hc_last_error().decode()
+
+    # creation and the model check, as the dynamics family's
+    assert "hc_create: num_envs" in reason(lib.hc_create(0, C.byref(he_model), g, 0, C.byref(h)))
+    assert "hc_create: null output" in reason(lib.hc_create(0, C.byref(he_model), g, 4, None))
+    assert "hc_create: null gravity" in reason(lib.hc_create(0, C.byref(he_model), None, 4, C.byref(h)))
+    assert "null model" in reason(lib.hc_create(0, None, g, 4, C.byref(h)))
+    assert h.value is None
+    assert lib.hc_validate_model(C.byref(he_model)) == 0
+    centroidal.validate_model(he_model)
+    m = copy.deepcopy(he_model)
+    m.num_bodies = 23
+    assert "bodies" in reason(lib.hc_validate_model(C.byref(m)))
+    with pytest.raises(centroidal.CentroidalError, match="bodies"):
+        centroidal.validate_model(m)
+    m = copy.deepcopy(he_model)
+    for b in range(1, NB):
+        m.parents[b] = b - 1  # one chain of 23 joints
+    assert "joints from the root" in reason(lib.hc_validate_model(C.byref(m)))
+    assert "joints from the root" in reason(lib.hc_create(0, C.byref(m), g, 4, C.byref(h)))
+    assert lib.hc_destroy(None) == 0
+
+    one, two = C.c_void_p(4096), C.c_void_p(8192)  # never dereferenced: every call below is refused first
+    block = C.create_string_buffer(4096)
+    fake = C.cast(block, C.c_void_p)
+
+    def outputs(**ptrs):
+        o = centroidal.HcOutputs()
+        for k, v in ptrs.items():
+            setattr(o, k, v)
+        return C.byref(o)
+
+    none, odd = outputs(), outputs(com=C.c_void_p(8194))
+    # each refusal, with everything after it in the order wrong as well: the earlier one is the one reported
+    assert "hc_compute: null handle" in reason(lib.hc_compute(None, None, None, None, None))
+    assert "hc_compute: null state pointer" in reason(lib.hc_compute(fake, None, one, None, None))
+    assert "hc_compute: null state pointer" in reason(lib.hc_compute(fake, one, None, none, None))
+    assert "hc_compute: null output struct" in reason(lib.hc_compute(fake, C.c_void_p(4097), one, None, None))
+    assert "hc_compute: no output buffer" in reason(lib.hc_compute(fake, C.c_void_p(4097), one, none, None))
+    assert "hc_compute: every buffer must be 4-byte aligned" in reason(lib.hc_compute(fake, one, one, odd, None))
+    assert "4-byte aligned" in reason(lib.hc_compute(fake, C.c_void_p(4097), one, outputs(cmm=two), None))
+    assert "4-byte aligned" in reason(lib.hc_compute(fake, one, C.c_void_p(4098), outputs(cmm=two), None))
+    for name in centroidal.OUTPUTS:  # every output pointer is looked at
+        assert "4-byte aligned" in reason(lib.hc_compute(fake, one, one, outputs(**{"com": two, "energy": two, name: C.c_void_p(8195)}), None))
+    assert block.raw == bytes(4096)  # the stand-in handle was never written
+    # a real handle needs a device
+    rc = lib.hc_create(0, C.byref(he_model), g, 4, C.byref(h))
+    if rc != 0:
+        assert "device" in lib.hc_last_error().decode().lower() or "hip" in lib.hc_last_error().decode().lower()
+    else:
+        assert "no output buffer" in reason(lib.hc_compute(h, one, one, none, None))
+        lib.hc_destroy(h)
+
+
+# ------------------------------------------------------------------ the binding and the facade
+class _NoCalls:
+    """Stands in for the library: any call is a failure of the check under test."""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"library call {name} before the argument check")
+
+
+def _unbound(n=3, device=None):
+    import torch
+    from humanoid_amd import centroidal
+    o = object.__new__(centroidal.Centroidal)
+    o.lib, o.h, o.engine = _NoCalls(), None, None
+    o.device, o.num_envs, o.armature, o.gravity = device or torch.device("cuda", 0), n, True, True
+    o.gravity_vector = (0.0, 0.0, -9.81)
+    return o
+
+
+def test_binding_follows_the_query_binding_rules():
+    import torch
+    from humanoid_amd import centroidal, dynamics, solve, task
+    cls, error = centroidal.Centroidal, centroidal.CentroidalError
+    assert issubclass(cls, _abi.QueryBinding) and cls is not _abi.QueryBinding
+    for name in ("__del__", "flags", "_flags", "_states", "_out"):
+        assert name not in vars(cls) and hasattr(cls, name), name
+    assert cls.LIBRARY.prefix == "hc" and cls.LIBRARY.error_cls is error and cls.LIBRARY.path == dynamics.LIB_PATH
+    assert cls.LIBRARY.prototypes is centroidal.HC_PROTOTYPES and cls.LIBRARY is not dynamics.Dynamics.LIBRARY
+    assert cls.NO_CPU_PATH.endswith("no CPU path")
+    assert centroidal.HC_SYMBOLS == tuple(centroidal.HC_PROTOTYPES)
+    assert issubclass(error, RuntimeError) and error.__module__ == centroidal.__name__
+    o = _unbound()
+    with pytest.raises(error, match="root_state") as e:
+        o._states(torch.zeros(3, 13), torch.zeros(3 * ND, 2))
+    assert not isinstance(e.value, (dynamics.DynamicsError, solve.SolveError, task.TaskError))
+    with pytest.raises(error, match="x: expected a torch tensor"):
+        centroidal.check_tensor(None, None, (1,), None, "x")
+
+
+def test_binding_checks_every_tensor_before_any_library_call():
+    import torch
+    from humanoid_amd import centroidal
+    n = 3
+    shapes = centroidal.output_shapes(n)
+    assert shapes == {"com": (3, 3), "com_vel": (3, 3), "momentum": (3, 6), "cmm": (3, 6, 75), "cmm_bias": (3, 6),
+                      "energy": (3, 2)}
+    o = _unbound(n)
+    with pytest.raises(centroidal.CentroidalError, match="no output"):
+        o.refresh_into()
+    for name, shape in shapes.items():
+        bad = {"CPU tensor": torch.zeros(shape), "wrong dtype": torch.zeros(shape, dtype=torch.float64),
+               "wrong shape": torch.zeros(shape[0] + 1, *shape[1:]), "not a tensor": np.zeros(shape, np.float32)}
+        for what, t in bad.items():
+            with pytest.raises(centroidal.CentroidalError, match=name + ":"):
+                o.refresh_into(**{name: t})
+    with pytest.raises(centroidal.CentroidalError, match="cmm"):
+        o.refresh_into(cmm=torch.zeros(n, 75, 6).transpose(1, 2))
+    # a bad tensor behind good ones is still found before anything is passed on (the device is the CPU here)
+    o = _unbound(n, torch.device("cpu"))
+    with pytest.raises(centroidal.CentroidalError, match="energy"):
+        o.refresh_into(com=torch.zeros(n, 3), energy=torch.zeros(n, 3))
+    with pytest.raises(centroidal.CentroidalError, match="no output"):
+        o.refresh(*[False] * 6)
+
+
+def test_the_two_one_liners():
+    import torch
+    o = _unbound(2, torch.device("cpu"))
+    gen = torch.Generator().manual_seed(5)
+    A = torch.randn(2, 3, 3, generator=gen)
+    o.cmm = torch.zeros(2, 6, 75)
+    o.cmm[:, 3:6, 3:6] = A @ A.transpose(1, 2) + torch.eye(3)
+    o.momentum = torch.randn(2, 6, generator=gen)
+    w = o.average_angular_velocity()
+    assert w.shape == (2, 3)
+    torch.testing.assert_close((o.cmm[:, 3:6, 3:6] @ w.unsqueeze(-1)).squeeze(-1), o.momentum[:, 3:6], rtol=1e-4, atol=1e-4)
+    o.com = torch.tensor([[1.0, 2.0, 0.981], [0.0, -1.0, 2.0 * 0.981 + 0.5]])
+    o.com_vel = torch.tensor([[0.5, -0.25, 3.0], [1.0, 1.0, 0.0]])
+    cp = o.capture_point()
+    want = torch.tensor([[1.0 + 0.5 * np.sqrt(0.1), 2.0 - 0.25 * np.sqrt(0.1)], [np.sqrt((2 * 0.981 + 0.5) / 9.81), -1.0 + np.sqrt((2 * 0.981 + 0.5) / 9.81)]])
+    torch.testing.assert_close(cp, want.float(), rtol=1e-6, atol=1e-6)
+    torch.testing.assert_close(o.capture_point(ground_z=0.5)[1], torch.tensor([np.sqrt(0.2), -1.0 + np.sqrt(0.2)]).float(),
+                               rtol=1e-6, atol=1e-6)
+
+
+def test_dynamics_creates_its_centroidal_object_on_first_use():
+    from humanoid_amd import dynamics
+    assert isinstance(dynamics.Dynamics.centroidal, property)
+    d = object.__new__(dynamics.Dynamics)
+    sentinel = object()
+    d._centroidal = sentinel
+    assert d.centroidal is sentinel
+
+
+def test_facade_calls_before_prepare_sim():
+    from humanoid_amd.isaacgym import gymapi
+    gym = gymapi.acquire_gym()
+    sim = gym.create_sim(0, -1, gymapi.SIM_PHYSX, gymapi.SimParams())
+    for which in ("com", "cmm", "nothing"):
+        with pytest.raises(RuntimeError, match="acquire_centroidal_tensor before prepare_sim"):
+            gym.acquire_centroidal_tensor(sim, "humanoid", which)
+    assert gym.refresh_centroidal_tensors(sim) is True  # before any acquire: a no-op that reports success
+    assert sim.dynamics is None and sim.centroidal_acquired == set()
+    assert "acquire_centroidal_tensor" in gymapi.__doc__ and "refresh_centroidal_tensors" in gymapi.__doc__
+
+
+# ------------------------------------------------------------------ the reference against its pins
+@pytest.fixture(scope="module")
+def ref(he_model):
+    """The four seeded states and the float64 references at them (computed once, left unchanged): the six
+    outputs, M without armature and c without gravity."""
+    root, dof = cases.random_state(4, np.random.default_rng(11), height=(1.0, 2.0), vel=1.0, ang=0.6, tilt=0.8)
+    sp = _abi.default_sim_params()
+    g = tuple(sp.gravity)
+    out = CR.evaluate(he_model, root, dof, g, np.float64)
+    _, M, c0 = DR.evaluate(he_model, root, dof, g, np.float64, armature=False, no_gravity=True)
+    qd = np.stack([DR.gen_velocity(root[e], dof[e]) for e in range(4)])
+    r = out["com"] - root[:, :3].astype(np.float64)
+    return dict(root=root, dof=dof, sp=sp, g=g, out=out, M=M, c0=c0, qd=qd, r=r, n=4,
+                mtot=float(np.array(he_model.mass[:NB], np.float32).astype(np.float64).sum()))
+
+
+def test_cmm_times_velocity_is_the_momentum(ref):
+    A, mom = ref["out"]["cmm"], ref["out"]["momentum"]
+    err = np.abs(np.einsum("nrc,nc->nr", A, ref["qd"]) - mom).max() / np.abs(mom).max()
+    print("A_G qd - momentum, relative:", err)
+    assert np.abs(mom[:, :3]).max() > 10.0 and np.abs(mom[:, 3:]).max() > 1.0
+    assert err < 5e-15
+    np.testing.assert_allclose(ref["out"]["com_vel"] * ref["mtot"], mom[:, :3], rtol=1e-14)
+    assert abs(ref["mtot"] - 73.995) < 1e-3
+
+
+def test_cmm_is_the_re_referenced_base_rows_of_the_mass_matrix(ref):
+    A = ref["out"]["cmm"]
+    worst = blocks = 0.0
+    for e in range(ref["n"]):
+        want = CR.reference_point_shift(ref["M"][e][0:6], ref["r"][e])
+        worst = max(worst, np.abs(A[e] - want).max() / np.abs(A[e]).max())
+        assert np.array_equal(want[0:3], ref["M"][e][0:3])
+        blocks = max(blocks, np.abs(A[e][0:3, 0:3] - ref["mtot"] * np.eye(3)).max() / ref["mtot"],
+                     np.abs(A[e][3:6, 0:3]).max() / ref["mtot"])
+        # the locked inertia: symmetric positive definite
+        Ic = A[e][3:6, 3:6]
+        assert np.abs(Ic - Ic.T).max() < 1e-13 and np.linalg.eigvalsh(0.5 * (Ic + Ic.T)).min() > 0.5
+    print("A_G - re-referenced M[0:6], relative:", worst, " mass block and zero block, relative to m:", blocks)
+    assert worst < 1e-15
+    assert blocks < 5e-15
+
+
+def test_cmm_bias_is_the_derivative_of_the_momentum_at_constant_velocity(he_model, ref):
+    """cmm_bias against a central difference of the momentum along the configuration flow at constant qd (the
+    root advanced by its velocities, R_b <- R_b exp([h u_b]x) for every joint), as tests/test_task.py
+    differences J(q) qd. float64, h = 1e-5: truncation h^2 |x'''| / 6 ~ 1e-10 of rates of a few kg m/s^2,
+    rounding 1e-16 |momentum| / h ~ 1e-9; held to 1e-8 of the largest |cmm_bias|. And against the header's
+    identity: the re-referenced base entries of the bias force without gravity."""
+    Mo = DR.Model(he_model, np.float64)
+    h = 1e-5
+    worst_fd = worst_id = 0.0
+    for e in range(ref["n"]):
+        root, dof, qd = ref["root"][e], ref["dof"][e], ref["qd"][e]
+        R, p = DR.fk(Mo, root, dof)
+        b = ref["out"]["cmm_bias"][e]
+
+        def momentum(s):
+            R2, p2 = np.zeros_like(R), np.zeros_like(p)
+            R2[0] = DR._exp(s * h * qd[3:6], np.float64) @ R[0]
+            p2[0] = p[0] + s * h * qd[0:3]
+            for bb in range(1, NB):
+                a = Mo.parents[bb]
+                Rl = R[a].T @ R[bb]  # the joint's rotation
+                R2[bb] = R2[a] @ Rl @ DR._exp(s * h * qd[6 + 3 * (bb - 1):9 + 3 * (bb - 1)], np.float64)
+                p2[bb] = p2[a] + R2[a] @ Mo.local_pos[bb]
+            return CR.momentum_of_pose(Mo, R2, p2, qd)
+
+        assert np.abs(momentum(0) - ref["out"]["momentum"][e]).max() < 1e-12
+        fd = (momentum(+1) - momentum(-1)) / (2 * h)
+        worst_fd = max(worst_fd, np.abs(fd - b).max() / np.abs(b).max())
+        want = CR.reference_point_shift(ref["c0"][e][0:6], ref["r"][e])
+        worst_id = max(worst_id, np.abs(want - b).max() / np.abs(b).max())
+        assert np.abs(b[:3]).max() > 5.0 and np.abs(b[3:]).max() > 0.5
+    print("cmm_bias against the central difference, relative:", worst_fd, " against the re-referenced bias:", worst_id)
+    assert worst_fd < 1e-8
+    assert worst_id < 2e-15
+    # at rest nothing is left
+    root, dof = ref["root"][:1].copy(), ref["dof"][:1].copy()
+    root[:, 7:13] = 0
+    dof[..., 1] = 0
+    rest = CR.evaluate(he_model, root, dof, ref["g"])
+    assert not rest["cmm_bias"].any() and not rest["momentum"].any() and rest["energy"][0, 0] == 0.0
+
+
+def test_momentum_and_energy_are_the_oracles(he_model, ref):
+    """P, L_G (the oracle's L_0 about the world origin moved to the centre of mass) and the kinetic energy
+    against oracle.momentum_energy: two float64 computations, so the bound is rounding. The potential to the
+    relative error of a float32 g, 2^-24."""
+    me = O.momentum_energy(he_model, ref["sp"], ref["root"], ref["dof"])
+    out = ref["out"]
+    P, L0 = me[:, 0:3], me[:, 3:6]
+    LG = L0 - np.cross(out["com"], P)
+    figs = dict(P=np.abs(P - out["momentum"][:, :3]).max() / np.abs(P).max(),
+                L=np.abs(LG - out["momentum"][:, 3:]).max() / np.abs(LG).max(),
+                kinetic=np.abs(me[:, 6] - out["energy"][:, 0]).max() / np.abs(me[:, 6]).max(),
+                potential=np.abs(me[:, 7] - out["energy"][:, 1]).max() / np.abs(me[:, 7]).max())
+    half = 0.5 * np.einsum("ni,nij,nj->n", ref["qd"], ref["M"], ref["qd"])
+    figs["half_qd_M_qd"] = np.abs(half - out["energy"][:, 0]).max() / np.abs(half).max()
+    print("against the oracle, relative:", figs)
+    assert figs["P"] < 2e-15 and figs["L"] < 1e-14 and figs["kinetic"] < 2e-15
+    assert figs["potential"] < 2.0 ** -24
+    assert figs["half_qd_M_qd"] < 3e-14
+    assert np.abs(out["energy"][:, 1]).min() > 500.0 and out["energy"][:, 0].min() > 40.0
+
+
+def test_float32_floors_are_where_the_tolerances_expect_them(he_model, ref):
+    """The floors the GPU tests multiply by 8, at these states: pinned inside a bracket so that 8 x a floor is
+    a real check and not a vacuous one, and a change of the reference that moves a floor is seen."""
+    _, floor = CR.floors(he_model, ref["root"], ref["dof"], ref["g"])
+    print("float32 floors:", {k: f"{v:.2e}" for k, v in floor.items()})
+    bracket = dict(com=(5e-8, 5e-6), com_vel=(1.5e-8, 1.5e-6), momentum=(5e-6, 5e-4), cmm=(5e-8, 5e-6),
+                   cmm_bias=(1e-6, 1e-4), kinetic=(5e-7, 5e-5), potential=(5e-5, 5e-3))
+    assert set(bracket) == set(CR.CHECKED)
+    for k, (lo, hi) in bracket.items():
+        assert lo < floor[k] < hi, (k, floor[k])
