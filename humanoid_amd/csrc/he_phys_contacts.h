@@ -204,17 +204,30 @@ HE_DEV int terrain_candidates(Lds& L, const GeomPrefetch& g, const Terrain& ter,
     }
     // a box keeps its 4 deepest corners (ties by index): a corner lane's rank among the 8 lanes
     // of its group, keys through xor swizzles (non-candidates keyed +inf never go first)
-    const float key = corner && tc.cand[0] ? tc.cd[0] : __builtin_inff();
-    int r = 0;
-    auto beat = [&](float kj, int sx) { r += (kj < key || (kj == key && (cc ^ sx) < cc)) ? 1 : 0; };
-    beat(swizzle_xor<1>(key), 1);
-    beat(swizzle_xor<2>(key), 2);
-    beat(swizzle_xor<3>(key), 3);
-    beat(swizzle_xor<4>(key), 4);
-    beat(swizzle_xor<5>(key), 5);
-    beat(swizzle_xor<6>(key), 6);
-    beat(swizzle_xor<7>(key), 7);
-    const bool kept0 = tc.cand[0] && (!corner || r < 4), kept1 = tc.cand[1];
+    // Only candidates beat a candidate, so a group of at most four candidates keeps them all whatever
+    // their order (a foot flat on the ground: its four bottom corners). The ranking runs only when some
+    // group holds five or more: the groups are the bytes of the candidates' ballot, counted in scalar
+    // code (a byte's count + 3 reaches bit 3 from five on).
+    bool kept0 = tc.cand[0];
+    const uint64_t cb = __ballot(corner && tc.cand[0]);
+    uint64_t cnt = cb - ((cb >> 1) & 0x5555555555555555ull);
+    cnt = (cnt & 0x3333333333333333ull) + ((cnt >> 2) & 0x3333333333333333ull);
+    cnt = (cnt + (cnt >> 4)) & 0x0F0F0F0F0F0F0F0Full;
+    const bool crowded = ((cnt + 0x0303030303030303ull) & 0x0808080808080808ull) != 0ull;
+    if (!HE_RANK_ON_DEMAND || __builtin_expect(crowded, 0)) {
+        const float key = corner && tc.cand[0] ? tc.cd[0] : __builtin_inff();
+        int r = 0;
+        auto beat = [&](float kj, int sx) { r += (kj < key || (kj == key && (cc ^ sx) < cc)) ? 1 : 0; };
+        beat(swizzle_xor<1>(key), 1);
+        beat(swizzle_xor<2>(key), 2);
+        beat(swizzle_xor<3>(key), 3);
+        beat(swizzle_xor<4>(key), 4);
+        beat(swizzle_xor<5>(key), 5);
+        beat(swizzle_xor<6>(key), 6);
+        beat(swizzle_xor<7>(key), 7);
+        kept0 = tc.cand[0] && (!corner || r < 4);
+    }
+    const bool kept1 = tc.cand[1];
     // the kept points take the body's slots in point index order (box corners by corner index),
     // so that resting contacts keep their slots from one substep to the next (the warm start then
     // maps impulses one to one); rank[] becomes that slot offset within the body
@@ -389,11 +402,12 @@ HE_DEV int reduce_overflow(Lds& L, const GeomPrefetch& g, const Terrain& ter, fl
 // Contact slots (oracle gen_contacts): joint limits, terrain (bodies in order, box corners
 // deepest-first), self pairs. Every contact generated is counted; when they exceed the capacity, the
 // limits stay and the contacts are reduced to the deepest ones, kept in slot order (reduce_overflow).
-// Writes the slots (cx, cn, cgap, cbb, ckey), tbase / tcnt, nc, nterr, nlim, ncand, and zeroes cf.
+// Writes the slots (cx, cn, cgap, cbb, ckey), tbase / tcnt, nc, nterr, nlim, ncand, and zeroes cf (the
+// launch's last physics step, `last`).
 // Scratch: IS (candidate records), lam (pair list), Ib / Ic (segments), Acc (bounding spheres).
 // Returns the contact slots in use.
 template <bool TGS>
-HE_DEV int gen_contacts(Lds& L, const GeomPrefetch& g, const he_sim_params& p, int tkind, int lane, Stamps& st) {
+HE_DEV int gen_contacts(Lds& L, const GeomPrefetch& g, const he_sim_params& p, int tkind, int lane, bool last, Stamps& st) {
     const int maxc = p.max_contacts < MAXC ? p.max_contacts : MAXC;
     const float off = p.contact_offset;
     const Terrain ter = terrain_of(p, tkind);
@@ -428,7 +442,9 @@ HE_DEV int gen_contacts(Lds& L, const GeomPrefetch& g, const he_sim_params& p, i
         nc = reduce_overflow<TGS>(L, g, ter, off, self_col, lane, maxc, nlim, terr_all, self_all, tc, st);
     STAMP(PH_SELF_SLOTS);
     if (lane == 0) { L.nc = nc; L.nlim = nlim; L.ncand = ncand_all; }
-    if (lane < NB) { L.cf[lane][0] = 0.f; L.cf[lane][1] = 0.f; L.cf[lane][2] = 0.f; }
+    // cf is stored once per launch, after its last step: that step alone zeroes it, before
+    // contact_forces_out adds the rows' impulses
+    if (lane < NB && reports(last)) { L.cf[lane][0] = 0.f; L.cf[lane][1] = 0.f; L.cf[lane][2] = 0.f; }
     sync();
     return nc;
 }

@@ -97,6 +97,26 @@ struct Lds {
 //   V    body velocities until bias_midpoint / the row set-up; tgs_bias_at's scratch after
 //   uf   PGS: midpoint velocity, then the solved velocity; TGS: the bias at the working velocity
 
+// Work that nothing reads, left out (DESIGN §4.1 "Unread work"), each piece behind a switch of its own
+// (1: left out, the default; 0: the parent's code, for tools/build_variant.py's A/B builds):
+//   HE_REPORT_LAST_ONLY  dof_force and contact_forces are stored once per launch, from what the last
+//        physics step left in LDS: the steps before it skip the iterations' drive sums, the drive and
+//        joint-limit force outputs, the rows' force directions and the zeroing of cf
+//   HE_LEG_ZROWS         the leg class of the <= 32-row TGS solve never reads Zh past dof KZ - 1: J^T's
+//        zero fill and sign pass stop there (he_phys_rows.h RowSystem::zshort)
+//   HE_RANK_ON_DEMAND    a box's corners are ranked only when some box has more than four candidates
+#ifndef HE_REPORT_LAST_ONLY
+#define HE_REPORT_LAST_ONLY 1
+#endif
+#ifndef HE_LEG_ZROWS
+#define HE_LEG_ZROWS 1
+#endif
+#ifndef HE_RANK_ON_DEMAND
+#define HE_RANK_ON_DEMAND 1
+#endif
+// whether a physics step computes the reported forces: the launch's last step (wave-uniform)
+HE_DEV bool reports(bool last) { return !HE_REPORT_LAST_ONLY || last; }
+
 // wave priority: s_setprio 3 over the serial chains (PGS rows, the elimination, the L^-T sweeps;
 // +2.8 % A/B, r01; the midpoint's L^-1 and L^-T sweeps, -1.2 % physics launch A/B, r04) against the
 // partner wave's throughput phases, 0 elsewhere

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/humanoid_engine.h"
 #include "he_math.h"
 #include "he_phys_contacts.h"
@@ -54,10 +56,10 @@ constexpr uint32_t block_bodies(int D) {
     for (int i = 32 * D; i < 32 * D + 32 && i < NG; ++i) m |= 1u << (i < 6 ? 0 : (i - 6) / 3 + 1);
     return m;
 }
-template <int D>
+template <int D, int DN = (NG + 31) / 32>  // dof blocks D .. DN - 1
 HE_DEV void zrows_block(regla::ZVec& z, uint32_t lb, const float (&b0)[3], const float (&b1)[3], const Lds& L, int l31,
                         int kh, bool rows32) {
-    if constexpr (32 * D < NG) {
+    if constexpr (D < DN && 32 * D < NG) {
         if (lb & block_bodies(D)) {
             float aS[3];
             const int j = 32 * D + l31;
@@ -82,11 +84,15 @@ HE_DEV void zrows_block(regla::ZVec& z, uint32_t lb, const float (&b0)[3], const
 #pragma unroll
             for (int i = 32 * D; i < 32 * D + 32 && i < NG; ++i) ZV(z, i) = 0.f;
         }
-        zrows_block<D + 1>(z, lb, b0, b1, L, l31, kh, rows32);
+        zrows_block<D + 1, DN>(z, lb, b0, b1, L, l31, kh, rows32);
     }
 }
+// zshort (wave-uniform, RowSystem::zshort): only dofs 0..KZ-1 are written, the block of the legs' dofs
+// with the signs of its bodies; z past them stays unwritten, for a solve that reads none of it. The
+// registers that are written get the full form's instructions on the full form's operands.
+constexpr int KZ = 32;  // the leg class's dofs (below: kLegBodies)
 HE_DEV void zrows_mfma(regla::ZVec& z, uint32_t lb, uint32_t anc0, uint32_t anc1, f3 rho, f3 dd, const Lds& L,
-                       int lane, bool rows32) {
+                       int lane, bool rows32, bool zshort) {
     const int l31 = lane & 31, kh = lane >> 5;
     float b0[3], b1[3];
     {
@@ -99,12 +105,22 @@ HE_DEV void zrows_mfma(regla::ZVec& z, uint32_t lb, uint32_t anc0, uint32_t anc1
             b1[st] = y;
         }
     }
-    zrows_block<0>(z, lb, b0, b1, L, l31, kh, rows32);
+    auto sign = [&](int B) { return (float)((anc0 >> B) & 1u) - (float)((anc1 >> B) & 1u); };
+    constexpr int BZ = (KZ - 1 - 6) / 3 + 2;  // the bodies of dofs 0..KZ-1
+    static_assert(KZ % 32 == 0 && KZ > 6 && BZ <= NB, "the short form is whole dof blocks");
+    zrows_block<0, KZ / 32>(z, lb, b0, b1, L, l31, kh, rows32);
     float sg[NB];
 #pragma unroll
-    for (int B = 0; B < NB; ++B) sg[B] = (float)((anc0 >> B) & 1u) - (float)((anc1 >> B) & 1u);
+    for (int B = 0; B < BZ; ++B) sg[B] = sign(B);
 #pragma unroll
-    for (int i = 0; i < NG; ++i) ZV(z, i) *= sg[i < 6 ? 0 : (i - 6) / 3 + 1];
+    for (int i = 0; i < KZ; ++i) ZV(z, i) *= sg[i < 6 ? 0 : (i - 6) / 3 + 1];
+    if (!zshort) {
+        zrows_block<KZ / 32>(z, lb, b0, b1, L, l31, kh, rows32);
+#pragma unroll
+        for (int B = BZ; B < NB; ++B) sg[B] = sign(B);
+#pragma unroll
+        for (int i = KZ; i < NG; ++i) ZV(z, i) *= sg[i < 6 ? 0 : (i - 6) / 3 + 1];
+    }
 }
 
 template <int I, int N = NG>
@@ -169,8 +185,7 @@ HE_DEV float zdot_lanes(const regla::ZVec& z, float yl, float y2) {
 // standing or walking on its feet): Zh is zero past dof 29, so the iterations' products run over the
 // first KZ = 32 dofs (dofs 30, 31 exact zeros) with Zh's other 44 registers dead. PhysArgs.full_dofs
 // (HE_TGS_LEGS=0 in the environment) turns the class off at run time.
-constexpr uint32_t kLegBodies = 0x1FFu;
-constexpr int KZ = 32;
+constexpr uint32_t kLegBodies = 0x1FFu;  // KZ: above zrows_mfma
 static_assert(smpl::kNB > 9, "the leg prefix is bodies 0..8");
 
 // Delassus operator on the matrix cores: A = Zh Zh^T as four 32x32 tiles of
@@ -338,9 +353,10 @@ HE_DEV int row_slot_again(bool act) {
 // against the old keys by readlane and fetches the impulse from lam_prev). Writes wckey (this solve's
 // keys), lam (the friction bound weight muw: mu, or mu r for the torsional row, parked in the impulse
 // words until the solve's set-up: a short live range through the rows' register peak) and row_dirs
-// (the row's linear direction for the reported forces; a joint limit's and a torsional row's: none).
+// (the row's linear direction for the reported forces; a joint limit's and a torsional row's: none;
+// written in the launch's last physics step only, `last`: no other step reports forces).
 // No sync at its end: the next phases read these words in the writing lane only.
-HE_DEV void row_setup(Lds& L, int lane, int nr, float mu, float lam_prev, RowDesc& r) {
+HE_DEV void row_setup(Lds& L, int lane, int nr, float mu, float lam_prev, bool last, RowDesc& r) {
     r.act = lane < nr;
     r.rs_ = r.act ? L.rslot[lane] : 0;
     r.kind = r.act ? L.rkind[lane] : 0;
@@ -385,7 +401,7 @@ HE_DEV void row_setup(Lds& L, int lane, int nr, float mu, float lam_prev, RowDes
     r.dd = r.kind == 0 ? ns : (r.kind == 1 ? t1 : (r.kind == 2 ? t2 : f3{0.f, 0.f, 0.f}));
     r.rho = r.kind == 3 ? np : cross3(r.kind == 0 ? xs : xp, r.dd);  // contact points about o
     L.lam[lane] = r.act && r.kind > 0 ? (r.kind == 3 ? mu * rp : mu) : 0.f;
-    if (r.act) {
+    if (r.act && reports(last)) {  // contact_forces_out, the only reader, runs in the launch's last step
         float* fr = row_dirs(L);
         const bool none = r.rb1 == -2;
         fr[3 * lane] = none ? 0.f : r.dd.x;
@@ -402,11 +418,19 @@ struct RowSystem {
     float brow;        // J_r uf + bias
     float diag;        // |zh_r|^2 = A[r][r]
     bool legs;         // every row's support inside the root and the legs (wave-uniform)
+    // legs, in a TGS kernel, with at most 32 rows (wave-uniform): z holds dofs 0..KZ-1 only, and
+    // ZV(z, i >= KZ) is unwritten (in every other case it holds all NG dofs, exact zeros outside the
+    // support). Whoever reads z past KZ has to exclude zshort first: row_system's limit rows and
+    // reductions, zbs (skips bodies outside lb), delassus_mfma<false> (dof groups of lb: none past dof 31)
+    // and solve_tgs<32> (legs_it) do; the wide solves, the wide Delassus forms, full_dofs and the PGS
+    // kernel's pgs_velocity read every dof and never see it set.
+    bool zshort;
 };
 // Contact rows, one per lane (oracle row_jacobian, contact_bias): z = J_r^T, brow = J_r uf + bias,
 // then z <- D^-1/2 L^-T z (dofs outside every row's support stay zero and are skipped
 // wave-uniformly), so that the Delassus operator A = Zh Zh^T is a plain Gram matrix of the lanes'
 // registers. Reads S, u0, yh, sDinv, Lp and the slots; writes no LDS.
+template <bool TGS>
 HE_DEV void row_system(Lds& L, const BodyTopo& T, const he_sim_params& p, bool full_dofs, int lane, int nr, float hs,
                        const RowDesc& r, RowSystem& s, Stamps& st) {
     using namespace regla;
@@ -417,18 +441,23 @@ HE_DEV void row_system(Lds& L, const BodyTopo& T, const he_sim_params& p, bool f
     const uint32_t lb = wave_or(anc0 | anc1);
     s.legs = (lb & ~kLegBodies) == 0u && !full_dofs;
     // z = J_r^T and brow = J_r u0 on the matrix cores
-    zrows_mfma(s.z, lb, anc0, anc1, r.rho, r.dd, L, lane, nr <= 32);
+    s.zshort = HE_LEG_ZROWS && TGS && s.legs && nr <= 32;
+    zrows_mfma(s.z, lb, anc0, anc1, r.rho, r.dd, L, lane, nr <= 32, s.zshort);
     // joint-limit rows: the stored row over the joint's three dofs (its support is the joint's
-    // ancestor chain, anc0)
+    // ancestor chain, anc0: under zshort a leg joint, its dofs below KZ)
     const bool limrow = r.act && r.rb1 == -2;
     if (__ballot(limrow)) {  // wave-uniform
         const int bl = limrow ? r.rb0 : 0;
         const float g3[3] = {L.cx[r.rs_][0], L.cx[r.rs_][1], L.cx[r.rs_][2]};
+        auto limit_dofs = [&](auto lo, auto hi) {
 #pragma unroll
-        for (int i = 0; i < NG; ++i) {
-            const float v = i < 6 ? 0.f : (bl == (i < 6 ? 0 : (i - 6) / 3 + 1) ? g3[i < 6 ? 0 : (i - 6) % 3] : 0.f);
-            ZV(s.z, i) = limrow ? v : ZV(s.z, i);
-        }
+            for (int i = decltype(lo)::value; i < decltype(hi)::value; ++i) {
+                const float v = i < 6 ? 0.f : (bl == (i < 6 ? 0 : (i - 6) / 3 + 1) ? g3[i < 6 ? 0 : (i - 6) % 3] : 0.f);
+                ZV(s.z, i) = limrow ? v : ZV(s.z, i);
+            }
+        };
+        limit_dofs(std::integral_constant<int, 0>{}, std::integral_constant<int, KZ>{});
+        if (!s.zshort) limit_dofs(std::integral_constant<int, KZ>{}, std::integral_constant<int, NG>{});
     }
     // J_r u0 on the register pairs (dof i into sum i mod 4); over the legs' dofs only when every
     // row's support is there (the dropped terms are fma(0, u, s) = s: the same bits)

@@ -249,7 +249,7 @@ struct TgsStep {
     int K;
     float hs, damp;
     bool last;       // the policy step's last substep
-    float tf1, tf2;  // the iterations' drive torques, summed per dof (lane, 64 + lane)
+    float tf1, tf2;  // the iterations' drive torques, summed per dof (lane, 64 + lane): the last substep only
 };
 // What follows a position iteration's velocity update: its drive torques, the positions by hs (the
 // last iteration: the step's output velocity), then (not the last) the next iteration's bias and
@@ -264,7 +264,8 @@ HE_DEV void tgs_advance(Lds& L0, const BodyTopo& T0, const he_sim_params& p, int
     const BodyTopo& T = WIDE ? L.T : T0;
     const int lane = WIDE ? phase_lane() : lane0;
     const bool lastit = it + 1 == ts.K;
-    tgs_drive_acc(L, lane, ts.tf1, ts.tf2);
+    // the drive sums feed tgs_drive_out alone, which only a reporting step runs (wave-uniform)
+    if (reports(ts.last)) tgs_drive_acc(L, lane, ts.tf1, ts.tf2);
     integrate_bodies(L, T, lane, p, ts.hs, ts.damp, L.u0, lastit, lastit && !ts.last);
     __builtin_amdgcn_sched_barrier(0);
     STAMP(PH_INTEGRATE);
@@ -318,6 +319,9 @@ HE_DEV void tgs_drive_out(Lds& L, int lane, const TgsStep& ts) {
 // are exact zeros. Precondition: NC == 32 (no row sits on lanes 32..63), and every lane >= nr
 // carries dl == 0 (its `act` is false) with a finite z, so that its products are +-0 and not NaN.
 // A change to how the inactive lanes are handled has to keep both.
+// Under legs_it the iterations read ZV(s.z, i) for i < KZ only (reduce_scatter_z_legs, zdot_lanes<KZ>):
+// RowSystem::zshort leaves the registers past them unwritten, so nothing here may read them without
+// excluding legs_it first (the wide instantiation never sees zshort set: it implies nr <= 32).
 template <int NC, bool EXT>
 HE_DEV float solve_tgs(Lds& L, const BodyTopo& T, const he_sim_params& p, int lane, int nr, const RowDesc& r,
                        const RowSystem& s, int nrb, float g0, float w0, TgsStep& ts, Stamps& st) {
@@ -425,8 +429,11 @@ HE_DEV float solve_tgs_rows(Lds& L, const BodyTopo& T, const he_sim_params& p, i
     else lamv = solve_tgs<MAXR, EXT>(L, T, p, lane, nr, r, s, nrb, g0, w0, ts, st);
     L.lam[lane] = r.act ? lamv : 0.f;
     if (lane == 0) L.nwc = p.warm_start ? nr : 0;
-    tgs_drive_out(L, lane, ts);
-    add_limit_force(L, lane, lamv, p.dt);  // limit row c = slot c
+    // dforce is stored from the launch's last step alone; the next step's drive_terms overwrites it
+    if (reports(ts.last)) {
+        tgs_drive_out(L, lane, ts);
+        add_limit_force(L, lane, lamv, p.dt);  // limit row c = slot c
+    }
     sync();
     return lamv;
 }
@@ -438,7 +445,8 @@ HE_DEV void tgs_free_iterations(Lds& L, const BodyTopo& T, const he_sim_params& 
         STAMP(PH_DU_SOLVE);
         tgs_advance<EXT>(L, T, p, lane, it, ts, st);
     }
-    tgs_drive_out(L, lane, ts);
+    if (reports(ts.last)) tgs_drive_out(L, lane, ts);
+    else sync();  // the ordering point tgs_drive_out ends on
 }
 
 // Projected Gauss-Seidel over the rows (pgs_sweep_fix): lane r keeps its unconstrained change, its
@@ -546,8 +554,8 @@ HE_DEV void pgs_drive_out(Lds& L, int lane, int nr, float dt) {
 }
 
 // Reported contact forces (net linear contact impulse per body / dt), lane = body: the output is the
-// last substep's, so the earlier substeps skip them (their cf rows stay zero, as gen_contacts set
-// them). Turns row_dirs into the per-row linear impulses (the stored directions x lambda).
+// last substep's, so the earlier substeps skip them (gen_contacts zeroes cf, and row_setup writes
+// row_dirs, in that substep alone). Turns row_dirs into the per-row linear impulses (the stored directions x lambda).
 HE_DEV void contact_forces_out(Lds&, int lane, int nc, bool act, float lamv, float dt) {
     Lds& L = phase_lds();  // the step's LDS base does not survive the iterations in a register
     float* fr = row_dirs(L);

@@ -32,7 +32,7 @@
 //          free_velocity) -> contact_forces_out, pgs_drive_out (last substep) -> integrate_bodies
 //   TGS    (solver_type 1) K position iterations of hs = dt / K on the step's factor and contact set:
 //          solve_tgs_rows (no rows: tgs_free_iterations), each iteration one sweep -> reduce_scatter_z
-//          -> tgs_velocity -> tgs_advance (tgs_drive_acc, integrate_bodies, every second iteration
+//          -> tgs_velocity -> tgs_advance (last substep: tgs_drive_acc; integrate_bodies, every second iteration
 //          tgs_bias_at, tgs_rhs); then tgs_drive_out, contact_forces_out (last substep)
 #include <hip/hip_runtime.h>
 
@@ -135,16 +135,16 @@ HE_DEV void substep(Lds& L0, const PhysArgs& a0, const he_model* mp, int lane,
     STAMP(PH_FREE_SOLVE);
     // the previous solve's impulses (lane = row) before the self-pair list reuses L.lam as scratch
     const float lam_prev = L.lam[lane];
-    const int nc = gen_contacts<TGS>(L, g, p, tkind, lane, st);
+    const int nc = gen_contacts<TGS>(L, g, p, tkind, lane, last, st);
     const int nr = build_rows(L, lane, nc);
     STAMP(PH_CONTACT_GEN);
     RowDesc rd;
-    row_setup(L, lane, nr, mu, lam_prev, rd);
+    row_setup(L, lane, nr, mu, lam_prev, last, rd);
     const float damp = TGS ? uniform(1.0f / (1.0f + dt * p.angular_damping)) : 1.0f / (1.0f + dt * p.angular_damping);
     TgsStep ts{K, hs, damp, last, 0.f, 0.f};
     if (nr > 0) {
         RowSystem rsys;
-        row_system(L, T, p, a.full_dofs, lane, nr, hs, rd, rsys, st);
+        row_system<TGS>(L, T, p, a.full_dofs, lane, nr, hs, rd, rsys, st);
         STAMP(PH_DELASSUS);
         float lamv;
         if constexpr (TGS) {

@@ -5,8 +5,8 @@ are counted for physics_kernel_tgs as a whole and for the <= 32-row position-ite
 total, SALU, s_and_saveexec, s_or exec restores, branches by kind, s_waitcnt.
 
 The iteration loops are the innermost natural loops (a backward branch and its target) that run
-the serial solves under a raised s_setprio: the <= 32-row class (solve_tgs<32>), the wide class (more
-v_pk_fma_f32 in its sweep) and the iterations without rows (none). A loop's span runs from its head
+the serial solves under a raised s_setprio: the <= 32-row class (solve_tgs<32>: 48 sweep rows, one
+v_med3_f32 each), the wide class (111 sweep rows) and the iterations without rows (none). A loop's span runs from its head
 to its backward branch, so a rare block that the layout moved behind the loop is not counted in it.
 
   python tools/control_skeleton.py [CODE_OBJECT] [-- extra hipcc flags]
@@ -94,8 +94,11 @@ def iteration_loops(ins):
     for a, b in sorted(inner):
         if not out or a > out[-1][1]:
             out.append((a, b))
-    # the free iterations run no sweep (no v_pk_fma_f32); the wide class's sweep issues more of them
-    return sorted(out, key=lambda ab: sum(op == "v_pk_fma_f32" for _, op, _, _ in ins[ab[0]:ab[1]]) or 1 << 30)
+    # by the rows the loop's sweeps hold, one v_med3_f32 (the row's clamp) each: the <= 32-row class sweeps 16 and
+    # 32 rows, the wide class 48 and 63; the free iterations run no sweep. (Not by v_pk_fma_f32: the <= 32-row
+    # sweep is the packed one, pgs_sweep_fix, and the wide one, pgs_sweep_tgs, issues scalar FMAs, so the count
+    # that was once read as "the wide class issues more" named the two loops the wrong way round.)
+    return sorted(out, key=lambda ab: sum(op == "v_med3_f32" for _, op, _, _ in ins[ab[0]:ab[1]]) or 1 << 30)
 
 
 def main():
