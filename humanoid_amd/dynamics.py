@@ -14,14 +14,14 @@ joints, not derivatives of the exp-map coordinates (the header has the definitio
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 from . import _abi
 
 from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_dynamics.h)
+from .build import LIBRARIES
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_dynamics.so")
+LIB_PATH = LIBRARIES["dynamics"].path
 JAC_ROWS = 6
 
 _V, _I = C.c_void_p, C.c_int

@@ -10,14 +10,14 @@ constructor raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import numpy as np
 
 from . import _abi
+from .build import LIBRARIES
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_engine.so")
+LIB_PATH = LIBRARIES["engine"].path
 
 
 class EngineError(RuntimeError):

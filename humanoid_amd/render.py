@@ -10,7 +10,6 @@ the constructor raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
 import zlib
 from typing import Sequence
@@ -18,8 +17,9 @@ from typing import Sequence
 import numpy as np
 
 from . import _abi
+from .build import LIBRARIES
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_render.so")
+LIB_PATH = LIBRARIES["render"].path
 
 # include/humanoid_render.h
 FLAG_SHADOWS, FLAG_CHECKER, FLAG_NO_CULL = 1, 2, 4

@@ -16,14 +16,14 @@ raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 from . import _abi
 
 from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_solve.h)
+from .build import LIBRARIES
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_solve.so")
+LIB_PATH = LIBRARIES["solve"].path
 MAX_RHS = 32
 
 _V, _I, _U = C.c_void_p, C.c_int, C.c_uint32

@@ -20,14 +20,14 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Optional
 
 from . import _abi
 
 from ._abi import FLAG_ARMATURE, FLAG_NO_GRAVITY, FLAGS_DEFAULT, NG  # noqa: F401  (include/humanoid_task.h)
+from .build import LIBRARIES
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhumanoid_task.so")
+LIB_PATH = LIBRARIES["task"].path
 MODE_FORCE, MODE_JOINT = 0, 1
 MODES = {"force": MODE_FORCE, "joint": MODE_JOINT}
 MAX_ROWS = 32

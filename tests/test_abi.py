@@ -103,16 +103,16 @@ def test_occupancy_guard_removes_the_rejected_object(tmp_path, monkeypatch):
     import subprocess
     import types
     from humanoid_amd import build
+    from resource_reports import at_budget
     src = tmp_path / "he_physics.hip"
     src.write_text("// fake")
     o = str(tmp_path / "he_physics.hip.o")
     stamp = o + ".cmd"
-    remark = ("remark: Function Name: physics_kernel\nremark:     VGPRs: 256\n"
-              "remark:     Occupancy [waves/SIMD]: 2\n"
-              "remark: Function Name: physics_kernel_tgs\nremark:     VGPRs: 300\n"
-              "remark:     Occupancy [waves/SIMD]: 1\n")
+    remark = at_budget("he_physics.hip", {"physics_kernel_tgs": {"occupancy": 1}})
+    ran = []
 
     def fake_run(cmd, capture_output=True, text=True):
+        ran.append(cmd)
         out = cmd[cmd.index("-o") + 1]
         with open(out, "w") as f:
             f.write("object")
@@ -122,61 +122,84 @@ def test_occupancy_guard_removes_the_rejected_object(tmp_path, monkeypatch):
     cmd = ["hipcc", "-c", str(src), "-o", o]
     with open(stamp, "w") as f:  # a stamp from an earlier build with the same command
         f.write(" ".join(cmd))
-    with pytest.raises(RuntimeError, match="occupancy 1"):
-        build._compile("hipcc", cmd, str(src), o, True, 0.0, False)
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: occupancy 1 waves/SIMD < 2"):
+        build._compile(cmd, str(src), o, True, 0.0, False)
     assert not os.path.exists(o) and not os.path.exists(stamp)
-    # a passing report keeps the object and writes the stamp
-    remark = remark.replace("SIMD]: 1", "SIMD]: 2")
-    assert build._compile("hipcc", cmd, str(src), o, True, 0.0, False)
+    # the twin is held to the occupancy too
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: occupancy 1 waves/SIMD < 2"):
+        build._compile(cmd, str(src), o, True, 0.0, False, product=False)
+    assert not os.path.exists(o) and not os.path.exists(stamp)
+    # a passing report keeps the object and writes the stamp: the command as given, run with the report's flag
+    full = remark = at_budget("he_physics.hip")
+    assert build._compile(cmd, str(src), o, True, 0.0, False)
     assert os.path.exists(o) and open(stamp).read() == " ".join(cmd)
-    # a watched kernel whose report has no occupancy line, or a missing kernel, fails too
-    full = remark
-    remark = full.replace("remark:     Occupancy [waves/SIMD]: 2\n", "", 1)
-    with pytest.raises(RuntimeError, match="no occupancy line"):
-        build._compile("hipcc", cmd, str(src), o, True, 0.0, False)
-    remark = full.split("remark: Function Name: physics_kernel_tgs")[0]
-    with pytest.raises(RuntimeError, match="2 expected"):
-        build._compile("hipcc", cmd, str(src), o, True, 0.0, False)
-
-
-def _spill_report(**kernels):
-    """A resource report in the compiler's words: kernel name -> (scratch bytes per lane, spilled VGPRs)."""
-    return "".join(f"remark: Function Name: _ZN12_GLOBAL__N_1{len(k)}{k}E8PhysArgs\nremark:     VGPRs: 256\n"
-                   f"remark:     ScratchSize [bytes/lane]: {b}\nremark:     Occupancy [waves/SIMD]: 2\n"
-                   f"remark:     SGPRs Spill: 65\nremark:     VGPRs Spill: {v}\n" for k, (b, v) in kernels.items())
+    assert ran[-1] == cmd + ["-Rpass-analysis=kernel-resource-usage"]
+    assert not build._compile(cmd, str(src), o, False, 0.0, False)  # up to date
+    # a kernel whose report has no occupancy line, or a missing kernel, fails too
+    remark = at_budget("he_physics.hip", {"physics_kernel": {"occupancy": None}})
+    with pytest.raises(RuntimeError, match="physics_kernel: no occupancy line"):
+        build._compile(cmd, str(src), o, True, 0.0, False)
+    assert not os.path.exists(o) and not os.path.exists(stamp)
+    remark = at_budget("he_physics.hip", without=["physics_kernel_tgs"])
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: not in the compiler's resource report"):
+        build._compile(cmd, str(src), o, True, 0.0, False)
+    # a failed compile leaves nothing behind either, and a source without entries is compiled without the report
+    remark = full
+    assert build._compile(cmd, str(src), o, True, 0.0, False)
+    monkeypatch.setattr(subprocess, "run", lambda cmd, **kw: types.SimpleNamespace(returncode=1, stderr="boom", stdout=""))
+    with pytest.raises(RuntimeError, match="hipcc failed for he_physics.hip"):
+        build._compile(cmd, str(src), o, True, 0.0, False)
+    assert not os.path.exists(o) and not os.path.exists(stamp)
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    remark = ""
+    other = str(tmp_path / "he_ingest.hip")
+    assert build._compile(["hipcc", "-c", other, "-o", o], other, o, True, 0.0, False)
+    assert ran[-1] == ["hipcc", "-c", other, "-o", o]
 
 
 def test_spill_ceilings_read_the_named_kernel():
-    """build._check_spills holds each kernel of MAX_SPILLS to its own ceilings, by exact mangled name:
-    physics_kernel never reads physics_kernel_tgs's block, and a kernel missing from the report fails."""
+    """build.check_resources holds each physics kernel to its own ceilings, by exact name: physics_kernel
+    never reads physics_kernel_tgs's block, and a kernel missing from the report fails."""
     from humanoid_amd import build
-    ceil_b, ceil_v = build.MAX_SPILLS["he_physics.hip"]["physics_kernel_tgs"]
-    assert build.MAX_SPILLS["he_physics.hip"]["physics_kernel"] == (0, 0) and ceil_b > 0 and ceil_v > 0
+    from resource_reports import at_budget
+    table = build.BUDGETS["he_physics.hip"]
+    _, ceil_b, ceil_v = table["physics_kernel_tgs"]
+    assert (ceil_b, ceil_v) == (148, 36) and table["physics_kernel"] == (2, 0, 0)
+    assert table["physics_kernel_ext"] == (2, 0, 0) and table["physics_kernel_tgs_ext"] == (2, 156, 38)
+    assert table["physics_order_kernel"] == table["warm_tu_kernel"] == (None, 0, None) and len(table) == 6
+
+    def check(changes=None, **kw):
+        build.check_resources("he_physics.hip", at_budget("he_physics.hip", changes, **kw))
+
     # both orders of the two blocks: the PGS kernel at 0 / 0, the TGS kernel at its ceiling
-    build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v)))
-    build._check_spills("he_physics.hip", _spill_report(physics_kernel_tgs=(ceil_b, ceil_v), physics_kernel=(0, 0)))
+    check()
+    check(order=["physics_kernel_tgs", "physics_kernel"] + [k for k in table if k not in ("physics_kernel_tgs", "physics_kernel")])
     with pytest.raises(RuntimeError, match=rf"physics_kernel_tgs: {ceil_b + 1} bytes/lane of scratch, {ceil_v} spilled"):
-        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b + 1, ceil_v)))
+        check({"physics_kernel_tgs": {"scratch": ceil_b + 1}})
     with pytest.raises(RuntimeError, match=rf"physics_kernel_tgs: {ceil_b} bytes/lane of scratch, {ceil_v + 1} spilled"):
-        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v + 1)))
-    with pytest.raises(RuntimeError, match="physics_kernel_tgs: no scratch size / spill count"):
-        build._check_spills("he_physics.hip", _spill_report(physics_kernel=(0, 0)))
-    with pytest.raises(RuntimeError, match="physics_kernel: no scratch size / spill count"):
-        build._check_spills("he_physics.hip", _spill_report(physics_kernel_tgs=(ceil_b, ceil_v)))
-    # a block without its spill line is a missing line, not a pass
-    cut = _spill_report(physics_kernel=(0, 0), physics_kernel_tgs=(ceil_b, ceil_v)).replace(
-        f"remark:     VGPRs Spill: {ceil_v}\n", "")
-    with pytest.raises(RuntimeError, match="physics_kernel_tgs: no scratch size / spill count"):
-        build._check_spills("he_physics.hip", cut)
+        check({"physics_kernel_tgs": {"spilled_vgprs": ceil_v + 1}})
+    with pytest.raises(RuntimeError, match="physics_kernel_tgs: not in the compiler's resource report"):
+        check(without=["physics_kernel_tgs"])
+    with pytest.raises(RuntimeError, match="physics_kernel: not in the compiler's resource report"):
+        check(without=["physics_kernel"])
+    # a block without its spill line, or its scratch line, is a missing line, not a pass
+    for line in ("spilled_vgprs", "scratch"):
+        with pytest.raises(RuntimeError, match="physics_kernel_tgs: no scratch size / spill count"):
+            check({"physics_kernel_tgs": {line: None}})
+    # each figure of each kernel, over its ceiling by one, fails and names its kernel alone
+    for kernel, (_, b, v) in table.items():
+        for over in ({"scratch": b + 1}, {"spilled_vgprs": v + 1} if v is not None else {"scratch": b + 2}):
+            with pytest.raises(RuntimeError) as e:
+                check({kernel: over})
+            assert str(e.value).startswith(f"{kernel}: {over.get('scratch', b)} bytes/lane of scratch")
     # only the TGS kernel exceeds: the error names it, in either order of the blocks, and never the PGS kernel
-    for order in (("physics_kernel", "physics_kernel_tgs"), ("physics_kernel_tgs", "physics_kernel")):
-        figures = {"physics_kernel": (0, 0), "physics_kernel_tgs": (ceil_b + 8, ceil_v + 2)}
+    for order in (list(table), list(table)[::-1]):
         with pytest.raises(RuntimeError) as e:
-            build._check_spills("he_physics.hip", _spill_report(**{k: figures[k] for k in order}))
+            check({"physics_kernel_tgs": {"scratch": ceil_b + 8, "spilled_vgprs": ceil_v + 2}}, order=order)
         assert str(e.value).startswith(f"physics_kernel_tgs: {ceil_b + 8} bytes/lane of scratch, {ceil_v + 2} spilled VGPRs")
-        assert f"{ceil_b} / {ceil_v}" in str(e.value)
-    # sources without ceilings are not checked
-    build._check_spills("hs_solve.hip", "")
+        assert f"{ceil_b} / {ceil_v}" in str(e.value) and "DESIGN §4.1" in str(e.value)
+    # sources without entries are not checked
+    build.check_resources("he_ingest.hip", "")
 
 
 def test_compile_command_is_the_builds():
@@ -187,14 +210,26 @@ def test_compile_command_is_the_builds():
     import sys
     from humanoid_amd import build
     common = ["--offload-arch=" + build.ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
-    libraries = [(build.SOURCES, {}), (build.SOURCES, build.PHASES_DEFS), (build.RENDER_SOURCES, {}),
-                 (build.DYNAMICS_SOURCES, {}), (build.SOLVE_SOURCES, {}), (build.TASK_SOURCES, {})]
-    assert [s for _, s, _ in build.LIBRARIES] == [s for s, _ in libraries]
-    assert [d for _, _, d in build.LIBRARIES] == [d for _, d in libraries]
+    # every source's flags spelled out here, not read from the table the build reads
+    engine = [("he_imitation.hip", ["-ffp-contract=off"]),
+              ("he_physics.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize",
+                                  "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+              ("he_ingest.hip", []), ("he_forces.hip", []), ("he_probe.hip", []),
+              ("he_rollout.hip", ["-ffp-contract=off"]), ("he_engine.cpp", ["-x", "hip"])]
+    libraries = [("libhumanoid_engine.so", engine, {}),
+                 ("libhumanoid_engine_phases.so", engine, {"he_physics.hip": ["-DHE_PHASE_STAMPS=1"]}),
+                 ("libhumanoid_render.so", [("hr_render.hip", [])], {}),
+                 ("libhumanoid_dynamics.so", [("hd_dynamics.hip", [])], {}),
+                 ("libhumanoid_solve.so", [("hs_solve.hip", ["-fno-slp-vectorize"])], {}),
+                 ("libhumanoid_task.so", [("ht_task.hip", ["-fno-slp-vectorize"])], {})]
+    assert [(lib.path, lib.sources, lib.defs) for lib in build.LIBRARIES.values()] == \
+        [(os.path.join(build.HERE, name), sources, defs) for name, sources, defs in libraries]
     n = 0
-    for sources, defs in libraries:
-        for src, flags in sources:
+    for lib, (_, sources, defs) in zip(build.LIBRARIES.values(), libraries):
+        assert len(lib.objects()) == len(sources)
+        for (src, flags), (obj_src, obj) in zip(sources, lib.objects()):
             o = os.path.join(build.BUILD, src + (".phases.o" if src in defs else ".o"))
+            assert (obj_src, obj) == (src, o)
             want = [build._hipcc()] + common + ["-cuid=" + hashlib.md5(src.encode()).hexdigest()[:16]] + flags + \
                 defs.get(src, []) + ["-c", os.path.join(build.CSRC, src), "-o", o]
             assert " ".join(build.compile_command(src, defs.get(src, ()), out=o)) == " ".join(want)

@@ -94,7 +94,7 @@ def test_library_exports_exactly_the_declared_symbols_of_both_families():
 
 def test_the_family_lives_in_the_dynamics_translation_unit():
     from humanoid_amd import build
-    assert [s for s, _ in build.DYNAMICS_SOURCES] == ["hd_dynamics.hip"] and len(build.LIBRARIES) == 6
+    assert [s for s, _ in build.LIBRARIES["dynamics"].sources] == ["hd_dynamics.hip"] and len(build.LIBRARIES) == 6
     assert any(h.endswith("humanoid_centroidal.h") for h in build.HEADERS)
     assert any(h.endswith("hd_centroidal.h") for h in build.HEADERS)
     src = open(os.path.join(build.CSRC, "hd_dynamics.hip")).read()
@@ -104,19 +104,20 @@ def test_the_family_lives_in_the_dynamics_translation_unit():
 
 def test_scratch_check_names_the_centroidal_kernel():
     from humanoid_amd import build
+    from resource_reports import report
 
-    def report(**scratch):
-        return "\n".join(f"remark: Function Name: _ZN12_GLOBAL__N_1{len(k)}{k}E\nremark:     ScratchSize [bytes/lane]: {v}"
-                         for k, v in scratch.items())
-
-    assert build.NO_SCRATCH_ALSO["hd_dynamics.hip"] == ("centroidal_kernel",)
-    build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0, centroidal_kernel=0))
-    with pytest.raises(RuntimeError, match="centroidal_kernel: 8 bytes"):
-        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0, centroidal_kernel=8))
+    assert build.BUDGETS["hd_dynamics.hip"] == {k: build.Budget(max_scratch=0) for k in ("dynamics_kernel", "centroidal_kernel")}
+    build.check_resources("hd_dynamics.hip", report({"dynamics_kernel": {}, "centroidal_kernel": {}}))
+    with pytest.raises(RuntimeError, match="centroidal_kernel: 8 bytes/lane of scratch"):
+        build.check_resources("hd_dynamics.hip", report({"dynamics_kernel": {}, "centroidal_kernel": {"scratch": 8}}))
+    with pytest.raises(RuntimeError, match="centroidal_kernel: not in the compiler's resource report"):
+        build.check_resources("hd_dynamics.hip", report({"dynamics_kernel": {}}))
     with pytest.raises(RuntimeError, match="centroidal_kernel: no scratch size"):
-        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=0))
-    with pytest.raises(RuntimeError, match="dynamics_kernel: 4 bytes"):  # the dynamics kernel is checked first
-        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=4, centroidal_kernel=8))
+        build.check_resources("hd_dynamics.hip", report({"dynamics_kernel": {}, "centroidal_kernel": {"scratch": None}}))
+    for order in (("dynamics_kernel", "centroidal_kernel"), ("centroidal_kernel", "dynamics_kernel")):
+        with pytest.raises(RuntimeError, match="dynamics_kernel: 4 bytes/lane of scratch"):  # the dynamics kernel is checked first
+            build.check_resources("hd_dynamics.hip", report({k: {"scratch": {"dynamics_kernel": 4, "centroidal_kernel": 8}[k]}
+                                                             for k in order}))
 
 
 # ------------------------------------------------------------------ refusals, no GPU

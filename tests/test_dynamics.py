@@ -178,11 +178,12 @@ def test_dynamics_library_exports_every_declared_symbol():
 
 def test_dynamics_library_is_not_part_of_the_engine():
     from humanoid_amd import build
-    assert not [s for s, _ in build.SOURCES + build.RENDER_SOURCES if s.startswith("hd_")]
-    assert [s for s, _ in build.DYNAMICS_SOURCES] == ["hd_dynamics.hip"]
-    assert len({build.DYNAMICS_LIB, build.LIB, build.RENDER_LIB, build.PHASES_LIB}) == 4
+    libs = build.LIBRARIES
+    assert [name for name, lib in libs.items() if any(s.startswith("hd_") for s, _ in lib.sources)] == ["dynamics"]
+    assert libs["dynamics"].sources == [("hd_dynamics.hip", [])]
+    assert len({libs[n].path for n in ("dynamics", "engine", "render", "engine_phases")}) == 4
     assert any(h.endswith("humanoid_dynamics.h") for h in build.HEADERS)
-    assert build.NO_SCRATCH["hd_dynamics.hip"] == "dynamics_kernel"
+    assert build.BUDGETS["hd_dynamics.hip"]["dynamics_kernel"] == build.Budget(max_scratch=0)
 
 
 def test_header_compiles_as_c_and_constants_match(tmp_path):
@@ -336,6 +337,6 @@ def test_engine_device_code_is_the_recorded_one():
     assert recs
     with open(recs[-1]) as f:
         want = json.load(f)["device_code"]
-    assert build.device_code_id(build.LIB) == want
-    ids = {build.device_code_id(p) for p in (build.LIB, build.RENDER_LIB, build.DYNAMICS_LIB)}
+    assert build.device_code_id(build.LIBRARIES["engine"].path) == want
+    ids = {build.device_code_id(build.LIBRARIES[n].path) for n in ("engine", "render", "dynamics")}
     assert len(ids) == 3

@@ -43,9 +43,13 @@ def test_render_library_is_not_part_of_the_engine():
     """The renderer is a library of its own: its sources are not among the engine's, and every header
     they include is tracked by the build."""
     from humanoid_amd import build
-    assert not [s for s, _ in build.SOURCES if s.startswith("hr_")]
-    assert [s for s, _ in build.RENDER_SOURCES] and build.RENDER_LIB != build.LIB
+    libs = build.LIBRARIES
+    assert [name for name, lib in libs.items() if any(s.startswith("hr_") for s, _ in lib.sources)] == ["render"]
+    assert libs["render"].sources == [("hr_render.hip", [])] and libs["render"].path != libs["engine"].path
     assert any(h.endswith("humanoid_render.h") for h in build.HEADERS)
+    # the render kernels (the template's two instantiations by their arguments) and the ray caster: no scratch
+    assert build.BUDGETS["hr_render.hip"] == {k: build.Budget(max_scratch=0)
+                                              for k in ("render_kernel<false>", "render_kernel<true>", "rays_kernel")}
 
 
 def test_camera_struct_and_constants_match_header(tmp_path):

@@ -69,32 +69,32 @@ def test_solve_library_exports_every_declared_symbol():
 
 def test_solve_library_is_a_library_of_its_own():
     from humanoid_amd import build
-    assert [s for s, _ in build.SOLVE_SOURCES] == ["hs_solve.hip"]
-    others = build.SOURCES + build.RENDER_SOURCES + build.DYNAMICS_SOURCES
-    assert not [s for s, _ in others if s.startswith("hs_")]
-    assert [s for s, _ in build.DYNAMICS_SOURCES] == ["hd_dynamics.hip"]
-    assert len({build.SOLVE_LIB, build.DYNAMICS_LIB, build.LIB, build.RENDER_LIB, build.PHASES_LIB}) == 5
+    libs = build.LIBRARIES
+    assert libs["solve"].sources == [("hs_solve.hip", ["-fno-slp-vectorize"])]
+    assert [name for name, lib in libs.items() if any(s.startswith("hs_") for s, _ in lib.sources)] == ["solve"]
+    assert libs["dynamics"].sources == [("hd_dynamics.hip", [])]
+    assert len({libs[n].path for n in ("solve", "dynamics", "engine", "render", "engine_phases")}) == 5
     assert any(h.endswith("humanoid_solve.h") for h in build.HEADERS)
-    assert set(build.NO_SCRATCH["hs_solve.hip"]) == {"solve_kernel", "torque_kernel"}
+    assert build.BUDGETS["hs_solve.hip"] == {k: build.Budget(max_scratch=0) for k in ("solve_kernel", "torque_kernel")}
     build.build()
-    ids = {build.device_code_id(p) for p in (build.LIB, build.RENDER_LIB, build.DYNAMICS_LIB, build.SOLVE_LIB)}
+    ids = {build.device_code_id(libs[n].path) for n in ("engine", "render", "dynamics", "solve")}
     assert len(ids) == 4
 
 
 def test_scratch_check_takes_one_name_or_several():
     from humanoid_amd import build
+    from resource_reports import report
 
-    def report(**scratch):
-        return "\n".join(f"remark: Function Name: _ZN12_GLOBAL__N_1{len(k)}{k}E\nremark:     ScratchSize [bytes/lane]: {v}"
-                         for k, v in scratch.items())
-
-    build._check_scratch("hs_solve.hip", report(solve_kernel=0, torque_kernel=0))
-    with pytest.raises(RuntimeError, match="torque_kernel: 8 bytes"):
-        build._check_scratch("hs_solve.hip", report(solve_kernel=0, torque_kernel=8))
+    build.check_resources("hs_solve.hip", report({"solve_kernel": {}, "torque_kernel": {}}))
+    build.check_resources("hs_solve.hip", report({"torque_kernel": {}, "solve_kernel": {}}))
+    with pytest.raises(RuntimeError, match="torque_kernel: 8 bytes/lane of scratch"):
+        build.check_resources("hs_solve.hip", report({"solve_kernel": {}, "torque_kernel": {"scratch": 8}}))
+    with pytest.raises(RuntimeError, match="torque_kernel: not in the compiler's resource report"):
+        build.check_resources("hs_solve.hip", report({"solve_kernel": {}}))
     with pytest.raises(RuntimeError, match="torque_kernel: no scratch size"):
-        build._check_scratch("hs_solve.hip", report(solve_kernel=0))
-    with pytest.raises(RuntimeError, match="dynamics_kernel: 4 bytes"):
-        build._check_scratch("hd_dynamics.hip", report(dynamics_kernel=4))
+        build.check_resources("hs_solve.hip", report({"solve_kernel": {}, "torque_kernel": {"scratch": None}}))
+    with pytest.raises(RuntimeError, match="dynamics_kernel: 4 bytes/lane of scratch"):
+        build.check_resources("hd_dynamics.hip", report({"dynamics_kernel": {"scratch": 4}}))
 
 
 # ------------------------------------------------------------------ argument errors, no GPU

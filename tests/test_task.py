@@ -78,21 +78,21 @@ def test_task_library_exports_exactly_the_declared_symbols():
 def test_task_library_is_an_extension_library_of_its_own():
     from humanoid_amd import build
     # one entry of the one table, its sources ht_task.hip alone; no other library lists an ht_ source
-    assert [[s for s, _ in sources] for lib, sources, _ in build.LIBRARIES if lib == build.TASK_LIB] == [["ht_task.hip"]]
-    assert not [s for lib, sources, _ in build.LIBRARIES if lib != build.TASK_LIB for s, _ in sources if s.startswith("ht_")]
-    assert len({lib for lib, _, _ in build.LIBRARIES}) == len(build.LIBRARIES) == 6
-    assert dict(build.TASK_SOURCES)["ht_task.hip"] == dict(build.SOLVE_SOURCES)["hs_solve.hip"] == ["-fno-slp-vectorize"]
+    libs = build.LIBRARIES
+    assert [s for s, _ in libs["task"].sources] == ["ht_task.hip"]
+    assert [name for name, lib in libs.items() if any(s.startswith("ht_") for s, _ in lib.sources)] == ["task"]
+    assert len({lib.path for lib in libs.values()}) == len(libs) == 6
+    assert dict(libs["task"].sources)["ht_task.hip"] == dict(libs["solve"].sources)["hs_solve.hip"] == ["-fno-slp-vectorize"]
     assert any(h.endswith("humanoid_task.h") for h in build.HEADERS)
     assert any(h.endswith("he_joint_space.h") for h in build.HEADERS)
-    assert build.NO_SCRATCH["ht_task.hip"] == "task_kernel"
-    assert build.MIN_OCCUPANCY["ht_task.hip"] == ("task_kernel", 2)
+    assert build.BUDGETS["ht_task.hip"] == {"task_kernel": build.Budget(min_waves=2, max_scratch=0)}
     # the compile line follows the others' rules: the common flags, an id from the file name, the source's flags
     import hashlib
     cmd = build.compile_command("ht_task.hip")
     assert "-cuid=" + hashlib.md5(b"ht_task.hip").hexdigest()[:16] in cmd and "-fno-slp-vectorize" in cmd
     assert cmd[-4:] == ["-c", os.path.join(build.CSRC, "ht_task.hip"), "-o", os.path.join(build.BUILD, "ht_task.hip.o")]
     build.build()
-    ids = {build.device_code_id(p) for p in (build.LIB, build.RENDER_LIB, build.DYNAMICS_LIB, build.SOLVE_LIB, build.TASK_LIB)}
+    ids = {build.device_code_id(libs[n].path) for n in ("engine", "render", "dynamics", "solve", "task")}
     assert len(ids) == 5
     # the shared header is included, not copied
     solve_src = open(os.path.join(build.CSRC, "hs_solve.hip")).read()

@@ -32,12 +32,11 @@ def main():
     B.build()
     out_dir = OUT_DIR
     os.makedirs(out_dir, exist_ok=True)
-    hipcc = B._hipcc()
     cmd, obj = variant_command(name, tu, defs)
     subprocess.run(cmd, check=True)
     objs = [obj if src == tu else os.path.join(B.BUILD, src + ".o") for src, _ in B.SOURCES]
     lib = os.path.join(out_dir, name + ".so")
-    subprocess.run([hipcc, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-o", lib] + objs, check=True)
+    subprocess.run([B._hipcc(), "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-o", lib] + objs, check=True)
     print(lib)
 
 

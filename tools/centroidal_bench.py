@@ -139,7 +139,7 @@ def main():
                hbm_peak_tb_per_s=HBM_PEAK_TBS, hbm_achievable_tb_per_s=HBM_ACHIEVABLE_TBS,
                bound="one wave per env runs a serial tree pass of 8 levels before it stores 1.9 KB: the launch is "
                      "bound by that latency and by the launch itself, not by HBM (see fraction_of_hbm_peak)",
-               dynamics_library_device_code_id=build.device_code_id(build.DYNAMICS_LIB),
+               dynamics_library_device_code_id=build.device_code_id(build.LIBRARIES["dynamics"].path),
                engine_device_code_id=build.device_code_id(build.LIB), results=results)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fo:

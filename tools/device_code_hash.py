@@ -35,4 +35,4 @@ if __name__ == "__main__":
     csrc = sys.argv[1] if len(sys.argv) > 1 else B.CSRC
     src = os.path.join(csrc, "he_physics.hip")
     print("product", code_hash(src, []))
-    print("phases ", code_hash(src, B.PHASES_DEFS["he_physics.hip"]))
+    print("phases ", code_hash(src, B.LIBRARIES["engine_phases"].defs["he_physics.hip"]))

@@ -84,7 +84,7 @@ def main():
         print(json.dumps(results[-1]), flush=True)
     rec = dict(tool="tools/dynamics_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
                launches=args.launches, repeats=args.repeats, store_rate_tb_per_s=STORE_RATE / 1e12,
-               dynamics_library_device_code_id=build.device_code_id(build.DYNAMICS_LIB), results=results)
+               dynamics_library_device_code_id=build.device_code_id(build.LIBRARIES["dynamics"].path), results=results)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)

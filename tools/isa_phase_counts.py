@@ -53,7 +53,7 @@ def cls(op):
 def main():
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "k.co")
-        subprocess.run(B.compile_command("he_physics.hip", B.PHASES_DEFS["he_physics.hip"], device_only=True, out=co),
+        subprocess.run(B.compile_command("he_physics.hip", B.LIBRARIES["engine_phases"].defs["he_physics.hip"], device_only=True, out=co),
                        check=True, capture_output=True)
         dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
                              capture_output=True, text=True).stdout

@@ -167,12 +167,12 @@ def queries(dirs):
     differs = False
     with tempfile.TemporaryDirectory() as tmp:  # 70 MB a side: not among the records
         outs = []
-        with_task = all(os.path.exists(os.path.join(d, "libhumanoid_task.so")) for d in dirs)
+        dynamics, solve, task = (os.path.basename(build.LIBRARIES[n].path) for n in ("dynamics", "solve", "task"))
+        with_task = all(os.path.exists(os.path.join(d, task)) for d in dirs)
         if not with_task:
-            print("no libhumanoid_task.so on both sides: the task library's outputs are left out", flush=True)
+            print(f"no {task} on both sides: the task library's outputs are left out", flush=True)
         for k, d in enumerate(dirs):
-            names = ("libhumanoid_dynamics.so", "libhumanoid_solve.so") + (("libhumanoid_task.so",) if with_task else ())
-            libs = [os.path.abspath(os.path.join(d, name)) for name in names]
+            libs = [os.path.abspath(os.path.join(d, name)) for name in (dynamics, solve) + ((task,) if with_task else ())]
             print(f"side {'AB'[k]}: {d}  device code: dynamics {build.device_code_id(libs[0])}, "
                   f"solve {build.device_code_id(libs[1])}" + (f", task {build.device_code_id(libs[2])}" if with_task else ""),
                   flush=True)

@@ -135,7 +135,7 @@ def main():
     rec = dict(tool="tools/render_bench.py", device=torch.cuda.get_device_name(0), warmup=args.warmup,
                launches=args.launches, envs=n, primitives_per_env=48, cases=args.cases,
                render_library=os.path.relpath(args.lib, ROOT) if args.lib else "humanoid_amd/libhumanoid_render.so",
-               render_library_device_code_id=build.device_code_id(args.lib or build.RENDER_LIB), results=results)
+               render_library_device_code_id=build.device_code_id(args.lib or build.LIBRARIES["render"].path), results=results)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)

@@ -111,7 +111,7 @@ def main():
         print(json.dumps(results[-1]), flush=True)
     rec = dict(tool="tools/solve_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
                calls_per_block=args.calls, blocks=args.blocks, body=args.body,
-               solve_library_device_code_id=build.device_code_id(build.SOLVE_LIB),
+               solve_library_device_code_id=build.device_code_id(build.LIBRARIES["solve"].path),
                engine_device_code_id=build.device_code_id(build.LIB), results=results)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fo:

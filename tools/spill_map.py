@@ -27,13 +27,13 @@ def main():
     kname = sys.argv[2] if len(sys.argv) > 2 else "physics_kernel"
     with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, "k.co")
-        extra = B.PHASES_DEFS["he_physics.hip"] + [f"-DHE_MIN_WAVES={w}", "-Rpass-analysis=kernel-resource-usage"]
+        extra = B.LIBRARIES["engine_phases"].defs["he_physics.hip"] + [f"-DHE_MIN_WAVES={w}", B.REPORT_FLAG]
         r = subprocess.run(B.compile_command("he_physics.hip", extra, device_only=True, out=co),
                            check=True, capture_output=True, text=True)
         dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
                              capture_output=True, text=True).stdout
-    # the kernel's block of the resource report, by its mangled name: <length><name>E<argument types>
-    report = next((b["fields"] for fn, b in B.resource_report(r.stderr).items() if re.search(r"\d" + kname + r"E", fn)), {})
+    # the kernel's block of the resource report, by its exact name
+    report = B.kernel_reports(r.stderr).get(kname, {}).get("fields", {})
     L = dis.split("\n")
     # the kernel's own disassembly: from its label to the next function label
     start = next(i for i, ln in enumerate(L) if re.search(r"\d" + kname + r"E\w*>:", ln))

@@ -121,8 +121,8 @@ def main():
                calls_per_block=args.calls, blocks=args.blocks,
                recipe="Dynamics.refresh(jacobian, bias) + row gather, Solver.solve, torch bmm / cholesky / cholesky_solve, "
                       "Solver.forward_dynamics; b = Jdot qd borrowed from the task library, untimed",
-               task_library_device_code_id=build.device_code_id(build.TASK_LIB),
-               solve_library_device_code_id=build.device_code_id(build.SOLVE_LIB),
+               task_library_device_code_id=build.device_code_id(build.LIBRARIES["task"].path),
+               solve_library_device_code_id=build.device_code_id(build.LIBRARIES["solve"].path),
                engine_device_code_id=build.device_code_id(build.LIB), results=results)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fo:
