@@ -148,8 +148,8 @@ def check_tensor(t, dtype, shape, device, what, error_cls, at_least=None):
 
 class QueryBinding:
     """What the bindings of the query libraries (``dynamics.Dynamics``, ``solve.Solver``,
-    ``task.TaskSpace``) share: an object on one engine that owns a library handle made from the engine's
-    model and gravity, launches on the engine's stream and reads the engine's live state unless a call
+    ``task.TaskSpace``, and the second families ``centroidal.Centroidal`` and ``ik.InverseKinematics``)
+    share: an object on one engine that owns a library handle made from the engine's model and gravity, launches on the engine's stream and reads the engine's live state unless a call
     names another. A subclass states ``LIBRARY`` (its :class:`Library`) and ``NO_CPU_PATH`` (the end of
     the constructor's refusal without a device) and adds the calls that are its own."""
     LIBRARY = None

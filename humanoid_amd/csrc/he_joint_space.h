@@ -37,7 +37,9 @@ struct Factor {
 
 // state -> S, F per column and the RNEA force per column. Params: the kernel's own argument block, of
 // which root [N,13], dof [N*69,2], qdd_des [N,69] (read when QDD) and flags are read. QDD: the joints'
-// accelerations P.qdd_des enter the bodies' accelerations (tree_kinematics).
+// accelerations P.qdd_des enter the bodies' accelerations (tree_kinematics). Without QDD, L.qdd is neither
+// read nor written here or in tree_kinematics: ht_task.hip's inverse kinematics keeps the root's world
+// position in L.qdd[0..2] across the call, so a change that touches L.qdd under !QDD has to move that.
 template <bool QDD, class Params>
 __device__ __forceinline__ void columns(Lds& L, const TreeModel& M, const Params& P, size_t env, int lane) {
     const TreeState S{L.q, L.u, L.qdd, L.R, L.P, L.W, L.Wd, L.A};

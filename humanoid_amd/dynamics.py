@@ -127,6 +127,16 @@ class Dynamics(_abi.QueryBinding):
         return self._task
 
     @property
+    def ik(self):
+        """The :class:`humanoid_amd.ik.InverseKinematics` of this engine (created on first use; its rows
+        stay set), with this object's ``armature`` setting; gravity does not enter it."""
+        if getattr(self, "_ik", None) is None:
+            from .ik import InverseKinematics
+            self._ik = InverseKinematics(self.engine, armature=self.armature)
+        self._ik.armature = self.armature
+        return self._ik
+
+    @property
     def centroidal(self):
         """The :class:`humanoid_amd.centroidal.Centroidal` of this engine (created on first use): centre of
         mass, momentum, the centroidal momentum matrix and the energies. It has no settings to hand over:

@@ -50,7 +50,11 @@ Engine-specific behaviour (documented, not silent):
 * ENGINE EXTENSION: the balance quantities in one launch (``include/humanoid_centroidal.h``):
   ``acquire_centroidal_tensor(sim, actor, which)`` for the centre of mass, its velocity, the momentum
   about the centre of mass, the centroidal momentum matrix [N,6,75], its rate term and the energies, and
-  ``refresh_centroidal_tensors``, which refreshes every acquired one.
+  ``refresh_centroidal_tensors``, which refreshes every acquired one;
+* ENGINE EXTENSION: inverse kinematics in one launch (``include/humanoid_ik.h``): ``set_ik_rows`` names up
+  to 32 rows (position components of points on bodies, orientation components of bodies), and
+  ``solve_inverse_kinematics`` gives the root and dof state, velocities zero, that puts them at their
+  targets, in the shapes the indexed state writes take. The sim's state is not touched.
 """
 from __future__ import annotations
 
@@ -561,6 +565,32 @@ class Gym:
                                    want_qdd=qdd_out_desc is not None)
         if joint:
             out.copy_(u[:, 6:])
+        return True
+
+    # -- inverse kinematics (engine extensions) -----------------------------------------------------
+    def set_ik_rows(self, sim: Sim, rows):
+        """Engine extension: the rows of ``solve_inverse_kinematics``, ``(body index or name, axis, point=(0, 0,
+        0))`` each: axis 0..2 is the world position component x / y / z of the point given in the body's frame,
+        3..5 a component of the body's orientation error. 1 to 32 rows, the same for every env; they replace
+        the rows set before (and are apart from ``set_task_rows``')."""
+        dyn = self._solve_dynamics(sim, "set_ik_rows")
+        dyn.ik.set_rows(rows)
+        return True
+
+    def solve_inverse_kinematics(self, sim: Sim, target_desc, root_out_desc, dof_out_desc, target_rot_desc=None,
+                                 iterations=8, damping=1e-4, step_clip=0.1, residual_desc=None):
+        """Engine extension: the pose that puts the ik rows at ``target`` [N,k] (and, for angular rows, the
+        bodies at the orientations ``target_rot`` [N,24,4], xyzw), from the current state in ``iterations``
+        steps of one launch (``include/humanoid_ik.h``). ``root_out`` [N,13] and ``dof_out`` [N*69,2] take the
+        pose with every velocity zero, as ``set_actor_root_state_tensor_indexed`` and
+        ``set_dof_state_tensor_indexed`` take them (the sim's own state tensors are refused: the state is
+        not touched); ``residual_desc`` [N,k] the rows' remaining errors. The dof angles stay within the
+        model's limits."""
+        dyn = self._solve_dynamics(sim, "solve_inverse_kinematics")
+        dyn.ik.solve(self._tensor(target_desc), None if target_rot_desc is None else self._tensor(target_rot_desc),
+                     iterations, damping, step_clip, root_out=self._tensor(root_out_desc),
+                     dof_out=self._tensor(dof_out_desc), want_residual=residual_desc is not None,
+                     residual=None if residual_desc is None else self._tensor(residual_desc))
         return True
 
     # -- balance quantities (engine extensions) -----------------------------------------------------
