@@ -61,7 +61,9 @@ LIBRARIES = {lib.name: lib for lib in (
     # the joint-space solves (include/humanoid_solve.h: forward dynamics, computed torque, M^-1 on a block of
     # vectors): a fourth library, which reads the engine's state buffers and includes the engine's
     # register algebra (he_regla.h) without being linked into it
-    # no SLP vectorisation, as for the physics kernel: the elimination issues its packed FMAs itself
+    # no SLP vectorisation, as for the physics kernel: the elimination issues its packed FMAs itself.
+    # The joint-reaction queries (include/humanoid_wrench.h, the hw_ entry points) are a second family of
+    # this library: device code in csrc/hs_wrench.h, run by torque_kernel itself
     Library("solve", [("hs_solve.hip", ["-fno-slp-vectorize"])]),
     # task-space control (include/humanoid_task.h: the task Jacobian rows, J M^-1, the operational-space
     # inertia and the task solve in one launch): a fifth product library, which shares the solve kernels'
@@ -134,7 +136,8 @@ BUDGETS = {
     # family of the translation unit (hd_centroidal.h) the lanes' columns in registers, everything indexed in LDS
     "hd_dynamics.hip": {"dynamics_kernel": Budget(max_scratch=0), "centroidal_kernel": Budget(max_scratch=0)},
     # the solve kernels hold the mass matrix and its factorisation in registers, within the 256 of two
-    # waves per SIMD
+    # waves per SIMD; the second query family of the translation unit (hs_wrench.h) adds no kernel: it is
+    # torque_kernel's run-time extension, staged in LDS that is dead by then
     "hs_solve.hip": {"solve_kernel": Budget(max_scratch=0), "torque_kernel": Budget(max_scratch=0)},
     # the task kernel is solve_kernel's shape and declares the same two waves
     "ht_task.hip": {"task_kernel": Budget(min_waves=2, max_scratch=0)},

@@ -17,6 +17,9 @@
 //              no factorisation: w = RNEA at qdd = (0; qdd_des), the base block of M is the composite
 //              inertia of the whole body (the root columns' F), a_b = M_bb^-1 (f_b - w_b) by a 6 x 6
 //              L D L^T in every lane, tau = w - f + M_jb a_b with M_jb a_b = F_j . (a_b as a motion vector).
+//              As hw_compute launches it (include/humanoid_wrench.h, hs_wrench.h) it also takes external
+//              wrenches on the bodies and a prescribed base acceleration, and writes every joint's wrench
+//              and every body's acceleration from what it has in LDS by then.
 // Spatial quantities of a subtree are referred to its own joint origin, never to a common far point: an
 // entry of M is then exact to float32 of the descendant's own inertia (see columns()).
 #include <hip/hip_runtime.h>
@@ -31,6 +34,7 @@
 #include "he_regla.h"
 #include "he_topo.h"
 #include "he_tree_state.h"
+#include "hs_wrench.h"
 
 namespace {
 
@@ -47,6 +51,13 @@ struct Params {
     float* base_acc;         // [N,6] or null
     int k;                   // 0: forward dynamics
     uint32_t flags;
+    // torque_kernel as hw_compute launches it (hs_wrench.h); all null from hs_computed_torque
+    const float* base_acc_in;  // [N,6]: the prescribed base acceleration, or null (free base)
+    const float* body_force;   // [N*24,3] or null
+    const float* body_torque;  // [N*24,3] or null
+    float* wrench;             // [N,24,6] or null
+    float* body_acc;           // [N,24,6] or null
+    int frame;                 // HW_FRAME_*
 };
 
 __global__ __launch_bounds__(kWave, 2) void solve_kernel(const Params P) {
@@ -113,45 +124,57 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
     const int lane = threadIdx.x;
     const size_t env = blockIdx.x;
     const TreeModel& M = *P.model;
-    columns<true>(L, M, P, env, lane);  // L.bias = w, the RNEA force at qdd = (0; qdd_des); ends on a barrier
+    if (P.qdd_des) {
+        columns<true>(L, M, P, env, lane);  // L.bias = w, the RNEA force at qdd = (0; qdd_des); ends on a barrier
+    } else {  // hw_compute without desired accelerations: everything at qdd = 0, which columns<false> is
+        for (int d = lane; d < ND; d += kWave) L.qdd[d] = 0.f;
+        columns<false>(L, M, P, env, lane);
+    }
+    if (P.body_force || P.body_torque) reaction_external(L, M, P, env, lane);
 
     // the base block of M: row i = (F_i's linear part, F_i's angular part) of root column i, the
     // composite inertia of the whole body about o. The same small solve in every lane.
     const float* f = P.gen_force ? P.gen_force + env * NG : nullptr;
-    float A[6][6], y[6];
+    float y[6];
+    if (P.base_acc_in) {  // prescribed base: no solve
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const v3 n = ld3(L.SF[i] + 6), p = ld3(L.SF[i] + 9);
-        A[i][0] = p.x, A[i][1] = p.y, A[i][2] = p.z, A[i][3] = n.x, A[i][4] = n.y, A[i][5] = n.z;
-        y[i] = (f ? f[i] : 0.f) - L.bias[i];
-    }
-    // A = Lb D Lb^T in place (lower triangle), then the two substitutions
-    float dinv[6];
+        for (int i = 0; i < 6; ++i) y[i] = P.base_acc_in[env * 6 + i];
+    } else {
+        float A[6][6];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float d = A[j][j];
-#pragma unroll
-        for (int s = 0; s < j; ++s) d -= A[j][s] * A[j][s] * A[s][s];
-        A[j][j] = d;
-        dinv[j] = 1.f / d;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            float v = A[i][j];
-#pragma unroll
-            for (int s = 0; s < j; ++s) v -= A[i][s] * A[j][s] * A[s][s];
-            A[i][j] = v * dinv[j];
+        for (int i = 0; i < 6; ++i) {
+            const v3 n = ld3(L.SF[i] + 6), p = ld3(L.SF[i] + 9);
+            A[i][0] = p.x, A[i][1] = p.y, A[i][2] = p.z, A[i][3] = n.x, A[i][4] = n.y, A[i][5] = n.z;
+            y[i] = (f ? f[i] : 0.f) - L.bias[i];
         }
+        // A = Lb D Lb^T in place (lower triangle), then the two substitutions
+        float dinv[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            float d = A[j][j];
+#pragma unroll
+            for (int s = 0; s < j; ++s) d -= A[j][s] * A[j][s] * A[s][s];
+            A[j][j] = d;
+            dinv[j] = 1.f / d;
+#pragma unroll
+            for (int i = j + 1; i < 6; ++i) {
+                float v = A[i][j];
+#pragma unroll
+                for (int s = 0; s < j; ++s) v -= A[i][s] * A[j][s] * A[s][s];
+                A[i][j] = v * dinv[j];
+            }
+        }
+#pragma unroll
+        for (int i = 1; i < 6; ++i)
+#pragma unroll
+            for (int s = 0; s < i; ++s) y[i] -= A[i][s] * y[s];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) y[i] *= dinv[i];
+#pragma unroll
+        for (int i = 4; i >= 0; --i)
+#pragma unroll
+            for (int s = i + 1; s < 6; ++s) y[i] -= A[s][i] * y[s];
     }
-#pragma unroll
-    for (int i = 1; i < 6; ++i)
-#pragma unroll
-        for (int s = 0; s < i; ++s) y[i] -= A[i][s] * y[s];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] *= dinv[i];
-#pragma unroll
-    for (int i = 4; i >= 0; --i)
-#pragma unroll
-        for (int s = i + 1; s < 6; ++s) y[i] -= A[s][i] * y[s];
 
     if (P.base_acc && lane < 6) {
         float v = y[0];
@@ -171,22 +194,26 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
             P.out[env * ND + d] = t;
         }
     }
+    if (P.wrench || P.body_acc) reaction_outputs(L, P, env, lane, v3{y[0], y[1], y[2]}, v3{y[3], y[4], y[5]});
 }
 
 }  // namespace
 
 struct hs_solver : QueryHandle<TreeModel> {};
+struct hw_reaction : QueryHandle<TreeModel> {};  // the second family's handle (include/humanoid_wrench.h)
 
 namespace {
 
-// The refusals the three entry points share, in the order the header lists them, around `own`, the
+// The refusals the entry points share, in the order the headers list them, around `own`, the
 // entry point's own; then the launch. Every buffer of the call is in P; the handle is read last.
-template <class Own>
-int launch(hs_solver* h, const char* who, void (*kernel)(Params), Params& P, void* stream, Own own) {
+template <class Handle, class Own>
+int launch(Handle* h, const char* who, void (*kernel)(Params), Params& P, void* stream, Own own) {
     if (check_call(who, h, P.root, P.dof)) return 1;
     if (own()) return 1;
     if (check_flags(who, P.flags, HS_FLAGS_ALL)) return 1;
-    if (check_aligned(who, {P.root, P.dof, P.gen_force, P.qdd_des, P.rhs, P.out, P.base_acc})) return 1;
+    if (check_aligned(who, {P.root, P.dof, P.gen_force, P.qdd_des, P.rhs, P.out, P.base_acc, P.base_acc_in, P.body_force,
+                            P.body_torque, P.wrench, P.body_acc}))
+        return 1;
     P.model = h->d_model;
     hipLaunchKernelGGL(kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
     HE_CHECK(hipGetLastError());
@@ -256,6 +283,48 @@ int hs_solve(hs_solver* h, const float* root_state, const float* dof_state, cons
         if (!out) return fail("hs_solve: null output buffer");
         if (rhs == out) return fail("hs_solve: rhs and out are the same buffer (the solve is not in place)");
         if (k < 1 || k > HS_MAX_RHS) return fail("hs_solve: k = %d outside 1..%d", k, HS_MAX_RHS);
+        return 0;
+    });
+}
+
+}  // extern "C"
+
+// ---- the joint-reaction queries (include/humanoid_wrench.h, the hw_ entry points): a second entry-point
+// family of this library on torque_kernel, whose device code is hs_wrench.h
+static_assert(HW_FLAG_ARMATURE == HS_FLAG_ARMATURE && HW_FLAG_NO_GRAVITY == HS_FLAG_NO_GRAVITY &&
+                  HW_FLAGS_ALL == HS_FLAGS_ALL,
+              "torque_kernel reads one set of flag bits");
+
+extern "C" {
+
+const char* hw_last_error(void) { return last_error(); }
+int hw_version(void) { return 1; }
+int hw_validate_model(const he_model* model) { return hs_validate_model(model); }
+
+int hw_create(int device, const he_model* model, const float gravity[3], int num_envs, hw_reaction** out) {
+    return query_create("hw_create", device, model, gravity, num_envs, out, hw_validate_model, fill_tree_model);
+}
+
+int hw_destroy(hw_reaction* h) { return query_destroy(h); }
+
+int hw_compute(hw_reaction* h, const float* root_state, const float* dof_state, const float* qdd_des,
+               const float* base_acc, const float* body_force, const float* body_torque, const hw_outputs* out,
+               int frame, uint32_t flags, void* stream) {
+    Params P{};
+    P.root = root_state;
+    P.dof = dof_state;
+    P.qdd_des = qdd_des;
+    P.base_acc_in = base_acc;
+    P.body_force = body_force;
+    P.body_torque = body_torque;
+    P.frame = frame;
+    P.flags = flags;
+    if (out) P.wrench = out->wrench, P.out = out->tau, P.base_acc = out->base_acc, P.body_acc = out->body_acc;
+    return launch(h, "hw_compute", torque_kernel, P, stream, [&] {
+        if (!out) return fail("hw_compute: null output struct");
+        if (!out->wrench && !out->tau && !out->base_acc && !out->body_acc) return fail("hw_compute: no output buffer");
+        if (frame != HW_FRAME_WORLD && frame != HW_FRAME_BODY)
+            return fail("hw_compute: frame %d outside 0..1 (HW_FRAME_WORLD, HW_FRAME_BODY)", frame);
         return 0;
     });
 }

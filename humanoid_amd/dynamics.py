@@ -146,6 +146,17 @@ class Dynamics(_abi.QueryBinding):
             self._centroidal = Centroidal(self.engine)
         return self._centroidal
 
+    @property
+    def reaction(self):
+        """The :class:`humanoid_amd.reaction.Reaction` of this engine (created on first use): the wrench
+        every joint transmits and the bodies' accelerations, with this object's ``armature`` and ``gravity``
+        settings."""
+        if getattr(self, "_reaction", None) is None:
+            from .reaction import Reaction
+            self._reaction = Reaction(self.engine, armature=self.armature)
+        self._reaction.armature, self._reaction.gravity = self.armature, self.gravity
+        return self._reaction
+
     def forward_dynamics(self, gen_force=None, out=None):
         """qdd [N,75] = M^-1 (gen_force - c) at the engine's current state: one launch, M never written."""
         return self.solver.forward_dynamics(gen_force, out)

@@ -179,6 +179,13 @@ class _Camera:
         self.follow_mode = FOLLOW_POSITION
 
 
+class ForceSensorProperties:
+    def __init__(self):
+        self.enable_forward_dynamics_forces = True
+        self.enable_constraint_solver_forces = True
+        self.use_world_frame = False
+
+
 class RigidBodyProperties:
     def __init__(self, mass, com, inertia):
         self.mass = float(mass)
@@ -249,6 +256,9 @@ class Sim:
         self.dynamics_acquired = set()  # of "jacobian", "mass_matrix", "bias"
         self.task_stage = None        # [N,75] the (0_6; tau) solve_task_space's joint mode writes
         self.centroidal_acquired = set()  # of humanoid_amd.centroidal.OUTPUTS
+        self.force_sensors = None     # humanoid_amd.sensors.ForceSensors, created by acquire_force_sensor_tensor
+        self.force_sensor_tensor = None  # [N*S,6]
+        self.force_sensor_dt = 0.0    # the simulated time of the last launch since the acquire
 
 
 # ----------------------------------------------------------------------------------- the Gym object
@@ -295,8 +305,20 @@ class Gym:
         except ValueError:
             return -1
 
-    def create_asset_force_sensor(self, asset: Asset, body_idx: int, pose: Transform):
-        asset.force_sensors.append((body_idx, pose))  # puffer-phc creates none
+    def create_asset_force_sensor(self, asset: Asset, body_idx: int, pose: Transform, props=None):
+        """A force sensor on body ``body_idx`` of every actor made from the asset, at ``pose`` in the body's
+        frame: it reads the wrench the body's parent joint transmits (``humanoid_amd/sensors.py`` defines the
+        reading). ``props``: a :class:`ForceSensorProperties`; both of its force switches must be on."""
+        props = ForceSensorProperties() if props is None else props
+        if not (props.enable_forward_dynamics_forces and props.enable_constraint_solver_forces):
+            raise NotImplementedError("force sensor: enable_forward_dynamics_forces and enable_constraint_solver_forces "
+                                      "must both be True (the reading is the whole joint wrench)")
+        body_idx = int(body_idx)
+        if body_idx == 0:
+            raise ValueError("force sensor on body 0: a sensor measures the body's parent joint, and the root has none")
+        if not 0 < body_idx < asset.model.num_bodies:
+            raise ValueError(f"force sensor: body {body_idx} outside 1..{asset.model.num_bodies - 1}")
+        asset.force_sensors.append((body_idx, copy.deepcopy(pose), bool(props.use_world_frame)))
         return len(asset.force_sensors) - 1
 
     def get_asset_dof_properties(self, asset: Asset):
@@ -450,7 +472,27 @@ class Gym:
         return self._acquire(sim, _abi.BUF_DOF_FORCE)
 
     def acquire_force_sensor_tensor(self, sim):
-        raise NotImplementedError("force sensors are not used by puffer-phc")
+        """[N*S,6]: per env the S sensors of the asset in their creation order, force 3 then torque 3, on
+        the body by its parent, in the sensor's frame (``use_world_frame``: world axes). Filled by
+        ``refresh_force_sensor_tensor`` for the step the last launch ran; zero before any."""
+        import torch
+        if sim.engine is None:
+            raise RuntimeError("acquire_force_sensor_tensor before prepare_sim")
+        if not sim.asset.force_sensors:
+            raise ValueError("acquire_force_sensor_tensor: the asset has no force sensor (create_asset_force_sensor)")
+        if sim.force_sensors is None:
+            from ..sensors import ForceSensors
+            if sim.dynamics is None:
+                from ..dynamics import Dynamics
+                sim.dynamics = Dynamics(sim.engine)
+            fs = sim.asset.force_sensors
+            poses = [[p.p.x, p.p.y, p.p.z, p.r.x, p.r.y, p.r.z, p.r.w] for _, p, _ in fs]
+            sim.force_sensors = ForceSensors(sim.engine, [b for b, _, _ in fs], poses, [w for _, _, w in fs],
+                                             reaction=sim.dynamics.reaction)
+            sim.force_sensor_tensor = torch.zeros(sim.engine.num_envs * len(fs), 6, dtype=torch.float32,
+                                                  device=sim.engine.device)
+        t = sim.force_sensor_tensor
+        return GymTensor(t.data_ptr(), t.shape, 1, sim.device, owner=t)
 
     # -- dynamics-query tensors -------------------------------------------------------------------
     def _acquire_dynamics(self, sim: Sim, actor_name: str, which: str):
@@ -519,6 +561,23 @@ class Gym:
         dyn.solver.computed_torque(self._tensor(qdd_des_desc), None, self._tensor(tau_out_desc),
                                    None if base_acc_desc is None else self._tensor(base_acc_desc),
                                    want_base_acc=base_acc_desc is not None)
+        return True
+
+    def solve_reaction_wrenches(self, sim: Sim, qdd_desc, wrench_out_desc, base_acc_desc=None, force_desc=None,
+                                torque_desc=None, frame="world"):
+        """Engine extension: wrench_out [N,24,6], the wrench every joint transmits (force 3, torque 3 about
+        the joint's own origin, on the body by its parent; row 0: what something outside must exert on the
+        root) for the joint accelerations qdd [N,69] (None: zero) at the current state
+        (``include/humanoid_wrench.h``). ``base_acc_desc`` [N,6] prescribes the base acceleration, None
+        leaves the base free; ``force_desc`` / ``torque_desc`` [N*24,3] are external forces at the bodies'
+        centres of mass and torques in world axes; ``frame`` "world" or "body"."""
+        dyn = self._solve_dynamics(sim, "solve_reaction_wrenches")
+
+        def opt(desc):
+            return None if desc is None else self._tensor(desc)
+
+        dyn.reaction.compute(opt(qdd_desc), opt(base_acc_desc), opt(force_desc), opt(torque_desc), frame, wrench=False,
+                             out={"wrench": self._tensor(wrench_out_desc)})
         return True
 
     def solve_mass_matrix(self, sim: Sim, rhs_desc, out_desc):
@@ -625,14 +684,24 @@ class Gym:
     def _flush(self, sim: Sim):
         if sim.pending_substeps:
             k, sim.pending_substeps = sim.pending_substeps, 0
+            if sim.force_sensors is not None:  # acquired force sensors read this launch's mean acceleration
+                sim.force_sensors.before_step()
+                sim.force_sensor_dt = k * float(sim.engine.params.dt)
             sim.engine.simulate(k)
 
     def refresh_dof_state_tensor(self, sim):
         self._flush(sim)
 
+    def refresh_force_sensor_tensor(self, sim):
+        """Flush, then fill the acquired force-sensor tensor for the launch that last ran. Before any
+        acquire: the flush alone."""
+        self._flush(sim)
+        if sim.force_sensors is not None:
+            sim.force_sensors.read(sim.force_sensor_dt, sim.force_sensor_tensor)
+        return True
+
     refresh_actor_root_state_tensor = refresh_dof_state_tensor
     refresh_rigid_body_state_tensor = refresh_dof_state_tensor
-    refresh_force_sensor_tensor = refresh_dof_state_tensor
     refresh_dof_force_tensor = refresh_dof_state_tensor
     refresh_net_contact_force_tensor = refresh_dof_state_tensor
 
