@@ -64,6 +64,48 @@ ACTUATION_PROTOTYPES = {
     "he_set_dof_actuation_forces": [C.c_void_p, C.c_void_p, C.c_void_p],
     "he_set_dof_actuation_forces_indexed": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
 }
+# include/humanoid_engine.h "env state": the packed per-env state and the sim-global scalars
+STATE_VERSION, STATE_MAX_FIELDS = 1, 16
+# a field's name by its buffer kind; the internal fields (kind -1) by their order in the layout
+STATE_FIELD_NAMES = {BUF_ROOT_STATE: "root", BUF_DOF_STATE: "dof_state", BUF_RB_STATE: "rb", BUF_CONTACT_FORCE: "cf",
+                     BUF_DOF_FORCE: "dof_force", BUF_DOF_TARGET: "targets", BUF_NUM_CONTACTS: "num_contacts",
+                     BUF_DROPPED_CONTACTS: "dropped", BUF_CONTACT_CACHE: "cache", BUF_INIT_ROOT_STATE: "init_root"}
+STATE_INTERNAL_NAMES = ("wrench", "dof_act")
+
+
+class HeStateField(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("offset_words", C.c_int32), ("words", C.c_int32), ("dtype", C.c_int32)]
+
+
+class HeStateLayout(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("words", C.c_int32), ("num_fields", C.c_int32),
+                ("fields", HeStateField * STATE_MAX_FIELDS)]
+
+
+class HeSimState(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("wrench_hold", C.c_int32), ("act_set", C.c_int32), ("launches", C.c_int64)]
+
+
+# (engine, layout); (engine, ids, k, packed, stream) twice; (engine, src ids, dst ids, k, stream); (engine, struct)
+STATE_PROTOTYPES = {
+    "he_state_layout_get": [C.c_void_p, C.c_void_p],
+    "he_save_envs": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "he_load_envs": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "he_clone_envs": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "he_get_sim_state": [C.c_void_p, C.c_void_p],
+    "he_set_sim_state": [C.c_void_p, C.c_void_p],
+}
+
+
+def state_fields(layout):
+    """``(words, {name: (offset, words, dtype)})`` of a :class:`HeStateLayout`, in the layout's order."""
+    fields, internal = {}, iter(STATE_INTERNAL_NAMES)
+    for f in layout.fields[:layout.num_fields]:
+        name = STATE_FIELD_NAMES[f.kind] if f.kind >= 0 else next(internal)
+        fields[name] = (int(f.offset_words), int(f.words), int(f.dtype))
+    return int(layout.words), fields
+
+
 # the solve probe: factor, y, n, out, stream
 PROBE_PROTOTYPES = {
     "he_probe_masked_solves": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],

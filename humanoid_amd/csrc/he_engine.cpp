@@ -43,6 +43,13 @@ static int stage_motion_tables(MotionTables& t, int64_t F, int M, const float* l
     return 0;
 }
 
+// One included buffer as the env-state kernel reads it (env_state_kernel below): where env 0's row
+// starts, the words of a row, and where the row lies in an env's packed state.
+struct StateField {
+    uint32_t* base;
+    int32_t words, offset;
+};
+
 struct he_engine {
     int device = 0;
     he_sim_params params{};
@@ -100,6 +107,10 @@ struct he_engine {
     DeviceArray<int32_t> d_modes;
     DeviceArray<float> dof_act;
     bool act_set = false;
+    // the packed env state (he_save_envs / he_load_envs / he_clone_envs): one StateField per buffer whose
+    // env_buffers() row says `state`, built by he_create_envs from that table
+    DeviceArray<StateField> state_desc;
+    int state_fields = 0, state_words = 0;
 
     ~he_engine() {
         if (order_ready) (void)hipEventDestroy(order_ready);
@@ -108,33 +119,42 @@ struct he_engine {
 
 namespace {
 // A per-env buffer of the engine: what he_get_buffer calls it (-1: internal), its array, rows per env,
-// columns (0: one-dimensional), element type and the byte every element starts as. The table drives
-// he_create_envs and he_get_buffer; a new buffer is a member of he_engine and a row here.
+// columns (0: one-dimensional), element type, the byte every element starts as, and whether its row is
+// part of an env's state (include/humanoid_engine.h "env state": the packed state is the rows that say
+// so, in this order). The table drives he_create_envs, he_get_buffer and the state layout; a new buffer
+// is a member of he_engine and a row here.
 struct EnvBuffer {
     int kind;
     DeviceBytes* mem;
     int rows, cols, dtype, fill;
-    size_t bytes(int N) const { return (size_t)N * rows * (cols ? cols : 1) * 4; }  // both dtypes: 4 bytes
+    bool state;
+    int words() const { return rows * (cols ? cols : 1); }            // per env; both dtypes: 4 bytes
+    size_t bytes(int N) const { return (size_t)N * words() * 4; }
 };
+
+constexpr int HE_META_WORDS = 8;  // the imitation kernel's per-env motion-metadata cache row
 
 std::vector<EnvBuffer> env_buffers(he_engine* h) {
     const int F32 = HE_DTYPE_F32, I32 = HE_DTYPE_I32, NB = HE_NUM_BODIES, ND = HE_NUM_DOF;
     return {
-        {HE_BUF_ROOT_STATE, &h->root, 1, 13, F32, 0},
-        {HE_BUF_DOF_STATE, &h->dof_state, ND, 2, F32, 0},
-        {HE_BUF_RB_STATE, &h->rb, NB, 13, F32, 0},
-        {HE_BUF_CONTACT_FORCE, &h->cf, NB, 3, F32, 0},
-        {HE_BUF_DOF_FORCE, &h->dof_force, ND, 0, F32, 0},
-        {HE_BUF_DOF_TARGET, &h->targets, 1, ND, F32, 0},
-        {HE_BUF_NUM_CONTACTS, &h->num_contacts, 1, 0, I32, 0},
-        {HE_BUF_DROPPED_CONTACTS, &h->dropped, 1, 0, I32, 0},
-        {HE_BUF_CONTACT_CACHE, &h->cache, 1, HE_CACHE_WORDS, F32, 0},
-        {HE_BUF_INIT_ROOT_STATE, &h->init_root, 1, 13, F32, 0},
-        {HE_BUF_PHYS_ORDER, &h->order, 1, 0, I32, 0},
-        {HE_BUF_PHYS_COST, &h->cost, 1, 0, I32, 0},
-        {-1, &h->meta_cache, 1, 8, I32, 0xFF},  // motion -1: empty
-        {-1, &h->wrench, NB, 6, F32, 0},
-        {-1, &h->dof_act, 1, ND, F32, 0},
+        {HE_BUF_ROOT_STATE, &h->root, 1, 13, F32, 0, true},
+        {HE_BUF_DOF_STATE, &h->dof_state, ND, 2, F32, 0, true},
+        {HE_BUF_RB_STATE, &h->rb, NB, 13, F32, 0, true},
+        {HE_BUF_CONTACT_FORCE, &h->cf, NB, 3, F32, 0, true},
+        {HE_BUF_DOF_FORCE, &h->dof_force, ND, 0, F32, 0, true},
+        {HE_BUF_DOF_TARGET, &h->targets, 1, ND, F32, 0, true},
+        {HE_BUF_NUM_CONTACTS, &h->num_contacts, 1, 0, I32, 0, true},
+        {HE_BUF_DROPPED_CONTACTS, &h->dropped, 1, 0, I32, 0, true},
+        {HE_BUF_CONTACT_CACHE, &h->cache, 1, HE_CACHE_WORDS, F32, 0, true},
+        {HE_BUF_INIT_ROOT_STATE, &h->init_root, 1, 13, F32, 0, true},
+        // scheduling hints whose values reach no result; the order is a permutation of the envs, which
+        // copying rows between envs would break
+        {HE_BUF_PHYS_ORDER, &h->order, 1, 0, I32, 0, false},
+        {HE_BUF_PHYS_COST, &h->cost, 1, 0, I32, 0, false},
+        // derived from the motion tables: invalidated for every env a state is written to, not copied
+        {-1, &h->meta_cache, 1, HE_META_WORDS, I32, 0xFF, false},  // motion -1: empty
+        {-1, &h->wrench, NB, 6, F32, 0, true},
+        {-1, &h->dof_act, 1, ND, F32, 0, true},
     };
 }
 }  // namespace
@@ -216,6 +236,22 @@ int he_set_model(he_engine* h, const he_model* model) {
 
 static int warm_kernels(int device);
 
+// The packed env state's layout, from the table alone (host only; no buffer need exist): the included
+// rows in table order, each at the offset the ones before it leave.
+static int state_layout(he_engine* h, he_state_layout* out) {
+    he_state_layout l{};
+    l.version = HE_STATE_VERSION;
+    for (const EnvBuffer& b : env_buffers(h)) {
+        if (!b.state) continue;
+        if (l.num_fields == HE_STATE_MAX_FIELDS)
+            return fail("env state: more than HE_STATE_MAX_FIELDS (%d) buffers in the state", HE_STATE_MAX_FIELDS);
+        l.fields[l.num_fields++] = he_state_field{b.kind, l.words, b.words(), b.dtype};
+        l.words += b.words();
+    }
+    *out = l;
+    return 0;
+}
+
 // allocates and initialises every per-env buffer; the caller releases them all when this fails
 static int init_env_buffers(he_engine* h, int N, const float* host_start_xy) {
     for (const EnvBuffer& b : env_buffers(h)) {
@@ -238,6 +274,18 @@ static int init_env_buffers(he_engine* h, int N, const float* host_start_xy) {
     std::vector<int32_t> ord((size_t)N);
     for (int e = 0; e < N; ++e) ord[e] = e;
     HE_CHECK(h->order.upload(ord.data(), ord.size()));
+    // the env-state kernel's view of the table: one StateField per included buffer
+    he_state_layout layout;
+    if (state_layout(h, &layout)) return 1;
+    std::vector<StateField> desc;
+    for (const EnvBuffer& b : env_buffers(h))
+        if (b.state) {
+            const he_state_field& f = layout.fields[desc.size()];
+            desc.push_back(StateField{static_cast<uint32_t*>(b.mem->get()), f.words, f.offset_words});
+        }
+    HE_CHECK(h->state_desc.assign(desc.data(), desc.size()));
+    h->state_fields = layout.num_fields;
+    h->state_words = layout.words;
     return 0;
 }
 
@@ -251,6 +299,8 @@ int he_create_envs(he_engine* h, int num_envs, const float* host_start_xy) {
     if (warm_kernels(h->device)) return 1;
     if (init_env_buffers(h, num_envs, host_start_xy)) {
         for (const EnvBuffer& b : env_buffers(h)) b.mem->release();  // as before the call: a retry is valid
+        h->state_desc.release();
+        h->state_fields = h->state_words = 0;
         return 1;
     }
     if (const char* v = std::getenv("HE_PHYS_ORDER")) h->order_every = std::atoi(v);
@@ -310,6 +360,106 @@ static int copy_rows(float* dst, const float* src, const int32_t* ids, int k, in
     return 0;
 }
 }  // namespace
+
+namespace {
+// The one kernel behind he_save_envs (PACK: env rows -> packed rows), he_load_envs (UNPACK: packed rows
+// -> env rows) and he_clone_envs (CLONE: env src[i] -> env dst[i]). Block x is the entry i, and thread
+// blockIdx.y * blockDim.x + threadIdx.x the word w of the entry's packed row: a wave's 64 lanes move 64
+// consecutive words of the packed row and, but where a field ends inside the wave, 64 consecutive words
+// of the buffer (256 B either side, the coalesced form; the rows are 13, 138, 312, ... words and an
+// env's packed row `W` words with W odd, so a row, a field and an env's share of a buffer start at any
+// word: one dword per lane takes every alignment alike). Past the packed row the next HE_META_WORDS
+// threads invalidate the written env's motion-metadata cache row (UNPACK and CLONE). An id outside
+// 0..num_envs-1 skips its entry, as copy_rows_kernel does; so does a CLONE entry with src == dst.
+enum { STATE_PACK = 0, STATE_UNPACK = 1, STATE_CLONE = 2 };
+constexpr int STATE_BLOCK = 256;
+
+static __global__ void env_state_kernel(const StateField* __restrict__ desc, int num_fields, int W,
+                                        int32_t* __restrict__ meta_cache, const int32_t* __restrict__ ids,
+                                        const int32_t* __restrict__ dst_ids, uint32_t* packed, int k, int num_envs,
+                                        int mode) {
+    const int i = blockIdx.x;
+    const int w = blockIdx.y * blockDim.x + threadIdx.x;
+    if (i >= k || w >= W + HE_META_WORDS) return;
+    const int from = ids ? ids[i] : i;                   // the env read (PACK, CLONE) or written (UNPACK)
+    const int to = mode == STATE_CLONE ? dst_ids[i] : from;
+    if (from < 0 || from >= num_envs || to < 0 || to >= num_envs) return;
+    if (mode == STATE_CLONE && from == to) return;
+    if (w >= W) {
+        if (mode != STATE_PACK) meta_cache[(size_t)to * HE_META_WORDS + (w - W)] = -1;
+        return;
+    }
+    int f = 0;  // the field of word w: the offsets ascend and the first is 0
+    while (f + 1 < num_fields && w >= desc[f + 1].offset) ++f;
+    const StateField d = desc[f];
+    const int c = w - d.offset;  // < d.words: the fields are contiguous and w < W
+    if (mode == STATE_PACK)
+        packed[(size_t)i * W + w] = d.base[(size_t)from * d.words + c];
+    else if (mode == STATE_UNPACK)
+        d.base[(size_t)from * d.words + c] = packed[(size_t)i * W + w];
+    else
+        d.base[(size_t)to * d.words + c] = d.base[(size_t)from * d.words + c];
+}
+
+// the refusals of the three calls in the header's order, then the launch
+static int move_env_state(he_engine* h, const int32_t* ids, const int32_t* dst_ids, int k, void* packed, int mode,
+                          void* stream, const char* what) {
+    if (!h) return fail("%s: null handle", what);
+    if (!h->num_envs) return fail("%s: no envs created", what);
+    if (mode == STATE_CLONE) {
+        if (!ids || !dst_ids) return fail("%s: null id array", what);
+    } else {
+        if (!packed) return fail("%s: null state buffer", what);
+        if (!ids && k != h->num_envs) return fail("%s: null ids (only k == num_envs may leave them out)", what);
+    }
+    if (k < 0 || k > h->num_envs) return fail("%s: k = %d outside 0..%d", what, k, h->num_envs);
+    if (misaligned({ids, dst_ids, packed})) return fail("%s: every buffer must be 4-byte aligned", what);
+    if (k == 0) return 0;
+    const dim3 grid(k, (h->state_words + HE_META_WORDS + STATE_BLOCK - 1) / STATE_BLOCK);
+    env_state_kernel<<<grid, STATE_BLOCK, 0, (hipStream_t)stream>>>(h->state_desc, h->state_fields, h->state_words,
+                                                                    h->meta_cache, ids, dst_ids,
+                                                                    static_cast<uint32_t*>(packed), k, h->num_envs, mode);
+    HE_CHECK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int he_state_layout_get(he_engine* h, he_state_layout* out) {
+    if (!h) return fail("he_state_layout_get: null handle");
+    if (!out) return fail("he_state_layout_get: null layout");
+    return state_layout(h, out);
+}
+
+int he_save_envs(he_engine* h, const int32_t* ids, int k, void* dst, void* stream) {
+    return move_env_state(h, ids, nullptr, k, dst, STATE_PACK, stream, "he_save_envs");
+}
+int he_load_envs(he_engine* h, const int32_t* ids, int k, const void* src, void* stream) {
+    return move_env_state(h, ids, nullptr, k, const_cast<void*>(src), STATE_UNPACK, stream, "he_load_envs");
+}
+int he_clone_envs(he_engine* h, const int32_t* src_ids, const int32_t* dst_ids, int k, void* stream) {
+    return move_env_state(h, src_ids, dst_ids, k, nullptr, STATE_CLONE, stream, "he_clone_envs");
+}
+
+int he_get_sim_state(he_engine* h, he_sim_state* out) {
+    if (!h) return fail("he_get_sim_state: null handle");
+    if (!h->num_envs) return fail("he_get_sim_state: no envs created");
+    if (!out) return fail("he_get_sim_state: null sim state");
+    *out = he_sim_state{HE_STATE_VERSION, h->wrench_hold, h->act_set ? 1 : 0, (int64_t)h->launches};
+    return 0;
+}
+int he_set_sim_state(he_engine* h, const he_sim_state* in) {
+    if (!h) return fail("he_set_sim_state: null handle");
+    if (!h->num_envs) return fail("he_set_sim_state: no envs created");
+    if (!in) return fail("he_set_sim_state: null sim state");
+    if (in->version != HE_STATE_VERSION)
+        return fail("he_set_sim_state: version %u, this library reads %d", in->version, HE_STATE_VERSION);
+    if (in->wrench_hold < 0 || in->launches < 0)
+        return fail("he_set_sim_state: negative wrench_hold or launches (%d, %lld)", in->wrench_hold, (long long)in->launches);
+    h->wrench_hold = in->wrench_hold;
+    h->act_set = in->act_set != 0;
+    h->launches = in->launches;
+    return 0;
+}
 
 // The env step's kernels (physics, imitation, motion ingestion, indexed row copies) each pay a
 // one-time first-dispatch cost (~0.4-0.8 ms per kernel on the MI355X; 16-30 ms under rocprofv3's
@@ -571,7 +721,7 @@ int he_refresh(he_engine* h, void* stream) {
 // new motion tables: the imitation kernel's per-env metadata cache (keyed by motion id) is stale
 static hipError_t invalidate_meta_cache(he_engine* h) {
     if (!h->num_envs) return hipSuccess;
-    return h->meta_cache.fill(0xFF, (size_t)h->num_envs * 8);
+    return h->meta_cache.fill(0xFF, (size_t)h->num_envs * HE_META_WORDS);
 }
 
 int he_load_motions(he_engine* h, int64_t F, int M, const float* gts, const float* grs, const float* lrs,

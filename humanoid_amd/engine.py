@@ -44,7 +44,7 @@ HE_PROTOTYPES = {
     "he_imitation_reset_step": [_V, _V, _V, _U64, _U64, _V, _V, _V, _V, _V, _V],
     "he_set_debug_stamps": [_V, _V], "he_set_eval": [_V, _V], "he_set_amp": [_V, _V], "he_set_fused_step": [_V, _I],
     "he_amp_observations": [_I, _V, _V, _V, _V, _V, _V, _V, _V, _V],
-    **_abi.FORCE_PROTOTYPES, **_abi.ACTUATION_PROTOTYPES, **_abi.PROBE_PROTOTYPES,
+    **_abi.FORCE_PROTOTYPES, **_abi.ACTUATION_PROTOTYPES, **_abi.STATE_PROTOTYPES, **_abi.PROBE_PROTOTYPES,
     # include/humanoid_rollout.h
     "he_rollout_store": [_V, _V, _I, _I64, _V, _V, _I64, _I32, _V],
     "he_rollout_order": [_V, _I64, _V, _I, _V],
@@ -299,6 +299,90 @@ class Engine:
     def clear_dof_actuation_forces(self):
         """Drop the actuation: the next launch runs the kernels without it."""
         _check(self.lib.he_set_dof_actuation_forces(self.h, None, self.stream))
+
+    # ------------------------------------------------------------------ env state: save, restore, clone
+    @property
+    def state_layout(self):
+        """he_state_layout_get, cached: ``(words, {name: (offset, words, dtype)})`` of an env's packed state
+        (include/humanoid_engine.h "env state"): the public buffers by their short names, then ``wrench``
+        and ``dof_act``, offsets and sizes in 4-byte words, dtype an ``_abi.DTYPE_*``."""
+        if getattr(self, "_state_layout", None) is None:
+            layout = _abi.HeStateLayout()
+            _check(self.lib.he_state_layout_get(self.h, C.byref(layout)))
+            self._state_layout = _abi.state_fields(layout)
+        return self._state_layout
+
+    def _env_ids(self, ids, what):
+        """(pointer, count) of int32 env ids [k], k <= num_envs; None: every env in order."""
+        import torch
+        if ids is None:
+            return None, self.num_envs
+        p = self._dev(ids, torch.int32, what)
+        if ids.dim() != 1 or ids.numel() > self.num_envs:
+            raise EngineError(f"{what}: expected int32 [k] with k <= {self.num_envs}, got {tuple(ids.shape)}")
+        return p, int(ids.numel())
+
+    def save_envs(self, ids=None, out=None):
+        """he_save_envs: the packed states int32 [k, W] of envs ``ids`` (int32 [k] on the device; None: all
+        envs in order), row i that of ``ids[i]``, into ``out`` or a fresh tensor. One launch, no sync."""
+        import torch
+        p_ids, k = self._env_ids(ids, "save_envs ids")
+        words = self.state_layout[0]
+        if out is None:
+            out = torch.empty((k, words), dtype=torch.int32, device=self.device)
+        p_out = self._dev(out, torch.int32, "save_envs out", (k, words))
+        _check(self.lib.he_save_envs(self.h, p_ids, k, p_out, self.stream))
+        return out
+
+    def load_envs(self, state, ids=None):
+        """he_load_envs: rows of a packed ``state`` int32 [k, W] into envs ``ids`` (None: all, in order)."""
+        import torch
+        p_ids, k = self._env_ids(ids, "load_envs ids")
+        p_state = self._dev(state, torch.int32, "load_envs state", (k, self.state_layout[0]))
+        _check(self.lib.he_load_envs(self.h, p_ids, k, p_state, self.stream))
+
+    def clone_envs(self, src_ids, dst_ids):
+        """he_clone_envs: env ``src_ids[i]`` copied to env ``dst_ids[i]`` (int32 [k] each). A dst that is also
+        a src of the same call is undefined; ``src == dst`` entries are no-ops."""
+        if src_ids is None or dst_ids is None:
+            raise EngineError("clone_envs: src_ids and dst_ids are both required")
+        p_src, k = self._env_ids(src_ids, "clone_envs src_ids")
+        p_dst, k_dst = self._env_ids(dst_ids, "clone_envs dst_ids")
+        if k != k_dst:
+            raise EngineError(f"clone_envs: {k} sources for {k_dst} destinations")
+        _check(self.lib.he_clone_envs(self.h, p_src, p_dst, k, self.stream))
+
+    def state_field(self, state, name):
+        """A typed view of field ``name`` of packed states int32 [k, W]: [k, words] float32 or int32,
+        sharing the tensor's memory (``state_field(s, "root")`` is the saved batch's root states [k, 13])."""
+        import torch
+        words, fields = self.state_layout
+        if name not in fields:
+            raise EngineError(f"state_field: no field {name!r}; the state has {', '.join(fields)}")
+        if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 \
+                or state.shape[1] != words:
+            raise EngineError(f"state_field: expected int32 [k, {words}] packed states")
+        off, n, dtype = fields[name]
+        v = state[:, off:off + n]
+        return v.view(torch.float32) if dtype == _abi.DTYPE_F32 else v
+
+    def sim_state(self) -> _abi.HeSimState:
+        """he_get_sim_state: the sim-global scalars behind the per-env rows (pending wrench's hold, whether
+        an actuation is set, physics launches so far)."""
+        s = _abi.HeSimState()
+        _check(self.lib.he_get_sim_state(self.h, C.byref(s)))
+        return s
+
+    def set_sim_state(self, s):
+        """he_set_sim_state from an ``_abi.HeSimState`` or a dict of its fields (``sim_state_dict``)."""
+        if not isinstance(s, _abi.HeSimState):
+            s = _abi.HeSimState(**{k: int(v) for k, v in dict(s).items()})
+        _check(self.lib.he_set_sim_state(self.h, C.byref(s)))
+
+    def sim_state_dict(self) -> dict:
+        """``sim_state()`` as plain ints, for a checkpoint."""
+        s = self.sim_state()
+        return {name: int(getattr(s, name)) for name, _ in _abi.HeSimState._fields_}
 
     # ------------------------------------------------------------------ motion library
     def load_motions(self, tables):

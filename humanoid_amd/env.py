@@ -369,6 +369,94 @@ class HumanoidPHC:
             self.extras["amp_obs"] = self.amp_obs
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 
+    # -- snapshots (engine extension; INTEGRATION.md "Snapshots and branching") ----------------
+    # the per-env tensors this class keeps beside the engine's state: a snapshot copies them whole, a
+    # clone copies their rows
+    _ENV_TENSORS = ("progress_buf", "_sampled_motion_ids", "_motion_start_times", "_motion_start_times_offset",
+                    "_global_offset", "_reset_u8", "_term_u8", "obs_buf", "rew_buf", "reward_raw")
+    _GENERATORS = ("_gen", "_noise_gen", "_push_gen")
+
+    def _env_tensors(self):
+        names = self._ENV_TENSORS + (("_amp_obs_buf", "_amp_obs_demo_buf") if self.cfg.use_amp_obs else ())
+        return {name: getattr(self, name) for name in names}
+
+    def save_state(self) -> dict:
+        """Everything a step reads, as plain tensors (copies, on the device), ints and byte tensors (the
+        generators' ``get_state()``), so that ``torch.save`` / ``torch.load`` round-trips it and
+        :meth:`load_state` continues on the same trajectory, bit for bit: the packed engine state of all envs
+        (``Engine.save_envs``) with the sim-global scalars, the per-env tensors of this class (progress, the
+        motion bookkeeping, the reset and terminate bytes, the observation, reward and AMP buffers), the push
+        state, the loaded motion ids and the motion library's sampling weights, and the random generators.
+        The configuration (``cfg``, the motion file, eval mode) is the caller's to keep: a state loads into
+        an env made from the same one."""
+        lib = self._motion_lib
+        d = {"version": _abi.STATE_VERSION, "num_envs": int(self.cfg.num_envs),
+             "engine": self.engine.save_envs(), "sim_state": self.engine.sim_state_dict(),
+             "flag_test": bool(self.flag_test), "flag_im_eval": bool(self.flag_im_eval),
+             "motion_sample_start_idx": int(self._motion_sample_start_idx),
+             "loaded_motion_ids": lib._curr_motion_ids.clone(),
+             "sampling_prob": lib._sampling_prob.clone(), "termination_history": lib._termination_history.clone(),
+             "push_step": int(self._push_step), "push_left": int(self._push_left),
+             "push_f": None if self._push_f is None else self._push_f.clone()}
+        d.update({name: t.clone() for name, t in self._env_tensors().items()})
+        for name in self._GENERATORS:  # the noise and push generators exist once they have drawn
+            g = getattr(self, name, None)
+            d["generator" + name] = None if g is None else g.get_state().clone()
+        d["generator_motion_lib"] = None if lib._gen is None else lib._gen.get_state().clone()
+        return d
+
+    def load_state(self, d: dict):
+        """Put back a :meth:`save_state` dict (of this env or of another made from the same configuration,
+        also after ``torch.load``): the next steps are the ones that followed the save."""
+        import torch
+        if d.get("version") != _abi.STATE_VERSION or d.get("num_envs") != self.cfg.num_envs:
+            raise ValueError(f"load_state: a version {d.get('version')} state of {d.get('num_envs')} envs; this env "
+                             f"reads version {_abi.STATE_VERSION} and has {self.cfg.num_envs} envs")
+        if (bool(d["flag_test"]), bool(d["flag_im_eval"])) != (bool(self.flag_test), bool(self.flag_im_eval)):
+            raise ValueError("load_state: the state was saved in the other mode (eval / training); toggle first")
+        dev = self.device
+        lib = self._motion_lib
+        ids = d["loaded_motion_ids"].to(dev)
+        if lib._curr_motion_ids is None or not torch.equal(lib._curr_motion_ids.to(dev), ids):
+            self._load(sample_idxes=ids)  # the motions the saved envs were tracking
+        lib._sampling_prob = d["sampling_prob"].to(dev).clone()
+        lib._termination_history = d["termination_history"].to(dev).clone()
+        self._motion_sample_start_idx = int(d["motion_sample_start_idx"])
+        for name, t in self._env_tensors().items():  # in place: the engine and the views keep their pointers
+            t.copy_(d[name].to(dev))
+        self.engine.load_envs(d["engine"].to(dev).contiguous())
+        self.engine.set_sim_state(d["sim_state"])
+        self._push_step, self._push_left = int(d["push_step"]), int(d["push_left"])
+        self._push_f = None if d["push_f"] is None else d["push_f"].to(dev).clone()
+        seeds = {"_gen": self.cfg.seed, "_noise_gen": self.cfg.seed + 7919, "_push_gen": self.cfg.seed + 104729}
+        for name in self._GENERATORS:
+            s = d["generator" + name]
+            if s is None:  # not drawn from at the save: as new
+                if hasattr(self, name):
+                    delattr(self, name)
+                continue
+            if not hasattr(self, name):
+                setattr(self, name, torch.Generator(device=dev).manual_seed(seeds[name]))
+            getattr(self, name).set_state(s.cpu())
+        if d["generator_motion_lib"] is not None and lib._gen is not None:
+            lib._gen.set_state(d["generator_motion_lib"].cpu())
+
+    @staticmethod
+    def _clone_rows(tensors, src, dst):
+        for t in tensors:
+            t[dst] = t[src]
+
+    def clone_envs(self, src_ids, dst_ids):
+        """Env ``src_ids[i]`` becomes env ``dst_ids[i]`` as well: the engine's state (``Engine.clone_envs``:
+        the same state, root x and y included, not a translated one) and the same rows of this class's per-env
+        tensors. The generators are global and stay. A dst that is also a src of the call is undefined."""
+        import torch
+        src = torch.as_tensor(src_ids, device=self.device).to(torch.int32).contiguous()
+        dst = torch.as_tensor(dst_ids, device=self.device).to(torch.int32).contiguous()
+        self.engine.clone_envs(src, dst)
+        rows = list(self._env_tensors().values()) + ([] if self._push_f is None else [self._push_f])
+        self._clone_rows(rows, src.long(), dst.long())
+
     # -- AMP (:1352-1357) --------------------------------------------------------------------
     @property
     def amp_obs(self):
@@ -620,6 +708,33 @@ class PHCPufferEnv:
             else:
                 info.append(reward_info)
         return self.observations, rew, self.terminals, self.truncations, info
+
+    # -- snapshots: HumanoidPHC's, with the tick (the step index he_env_step hashes the reset draws from)
+    # and the episode bookkeeping of this class
+    _ENV_TENSORS = ("terminals", "truncations", "masks", "actions", "episode_returns", "episode_lengths")
+
+    def save_state(self) -> dict:
+        d = self.env.save_state()
+        d.update({"tick": int(self.tick), "episode_count": int(self.episode_count),
+                  "raw_rewards": self.raw_rewards.clone(), "acc": self._acc.clone()})
+        d.update({"puffer_" + name: getattr(self, name).clone() for name in self._ENV_TENSORS})
+        return d
+
+    def load_state(self, d: dict):
+        self.env.load_state(d)
+        dev = self.env.device
+        self.tick, self.episode_count = int(d["tick"]), int(d["episode_count"])
+        self.raw_rewards.copy_(d["raw_rewards"].to(dev))
+        self._acc.copy_(d["acc"].to(dev))
+        for name in self._ENV_TENSORS:
+            getattr(self, name).copy_(d["puffer_" + name].to(dev))
+
+    def clone_envs(self, src_ids, dst_ids):
+        import torch
+        self.env.clone_envs(src_ids, dst_ids)
+        src = torch.as_tensor(src_ids, device=self.env.device).long()
+        dst = torch.as_tensor(dst_ids, device=self.env.device).long()
+        self.env._clone_rows([getattr(self, name) for name in self._ENV_TENSORS], src, dst)
 
     def fetch_amp_obs_demo(self):  # env.py:206-207
         return self.env.fetch_amp_obs_demo()

@@ -762,6 +762,29 @@ class Gym:
         sim.engine.apply_body_forces_at_pos(self._tensor(force_desc), self._tensor(pos_desc), int(space), hold=1)
         return True
 
+    # -- env state: save, restore, clone (engine extensions; INTEGRATION.md "Snapshots and branching") --
+    # Each flushes the batched simulate() calls first, like a tensor write. An acquired force-sensor or
+    # dynamics tensor is stale until its next refresh.
+    def save_env_states(self, sim: Sim, ids_desc=None):
+        """The packed states int32 [k, W] of envs ``ids`` (an int32 descriptor; None: every env in order) as
+        a descriptor of a fresh tensor (``gymtorch.wrap_tensor`` gives the tensor itself)."""
+        from . import gymtorch
+        self._flush(sim)
+        return gymtorch.unwrap_tensor(sim.engine.save_envs(None if ids_desc is None else self._tensor(ids_desc)))
+
+    def load_env_states(self, sim: Sim, state_desc, ids_desc=None):
+        """Rows of packed states (``save_env_states``) into envs ``ids`` (None: every env in order)."""
+        self._flush(sim)
+        sim.engine.load_envs(self._tensor(state_desc), None if ids_desc is None else self._tensor(ids_desc))
+        return True
+
+    def clone_env_states(self, sim: Sim, src_ids_desc, dst_ids_desc):
+        """Env ``src_ids[i]`` copied to env ``dst_ids[i]`` (int32 descriptors), the whole state, root x and y
+        included. A dst that is also a src of the call is undefined."""
+        self._flush(sim)
+        sim.engine.clone_envs(self._tensor(src_ids_desc), self._tensor(dst_ids_desc))
+        return True
+
     # -- stepping -----------------------------------------------------------------------------------
     def simulate(self, sim: Sim):
         sim.pending_substeps += 1

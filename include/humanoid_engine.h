@@ -301,6 +301,56 @@ int he_set_dof_drive_modes(he_engine* h, const int32_t* host_modes);
 int he_set_dof_actuation_forces(he_engine* h, const float* src, void* stream);
 int he_set_dof_actuation_forces_indexed(he_engine* h, const float* src, const int32_t* ids, int k, void* stream);
 
+/* ---------------- env state: save, restore, clone (engine extension) -------------------- */
+/* An env's state is every per-env buffer the step reads back, public or internal: root, dof state,
+ * rigid-body rows, contact and dof forces, dof targets, the contact counts, the warm-start cache,
+ * HE_BUF_INIT_ROOT_STATE, the pending external wrench rows and the actuation rows. Its PACKED form is
+ * those rows concatenated in the engine's buffer-table order, `words` 4-byte words per env (the layout
+ * query gives the offsets; they follow the table and may grow with it, so a stored state is read with
+ * the layout of the build that wrote it: he_state_layout.version changes when a field's meaning does).
+ * Not in the state:
+ *   - HE_BUF_PHYS_ORDER / HE_BUF_PHYS_COST: scheduling hints whose values reach no result; the order
+ *     is a permutation of the envs and stays one because no call here touches either buffer;
+ *   - the imitation kernel's per-env motion-metadata cache: derived from the motion tables, keyed by
+ *     the env's motion id. It is INVALIDATED (0xFF) for every env he_load_envs / he_clone_envs write,
+ *     in the same launch, never copied: the env's next imitation step re-reads the tables.
+ * The motion library, the model, the drive modes, the sim parameters and the caller-owned buffers
+ * (he_set_env_properties, he_env_motion, eval, AMP) are not per-env engine state and are the caller's to
+ * keep; the few sim-global scalars the step reads are he_sim_state below.
+ *
+ * he_state_layout_get: host only, no device call; valid on any handle, with or without envs (the
+ * layout is a property of the build). Fields are contiguous, in table order; kind is the he_buf_kind,
+ * -1 for an internal buffer (the wrench rows, then the actuation rows). Refusals: null handle, null out.
+ *
+ * he_save_envs / he_load_envs / he_clone_envs: ONE launch each on the caller's stream, no host
+ * synchronisation. ids (and src_ids / dst_ids) are DEVICE int32 [k], as in the indexed writes; row i of
+ * the packed array (DEVICE, [k, words] words) belongs to env ids[i]. An id outside 0..N-1 skips its
+ * row and writes nothing (in a clone: either id). NULL ids with k == N mean every env in order. A
+ * repeated id in he_load_envs, or a repeated dst in he_clone_envs, leaves one of the rows, which one is
+ * undefined. he_clone_envs copies env src_ids[i] to env dst_ids[i]; an entry with src == dst is a
+ * no-op; a dst that is also a src of the same call is UNDEFINED (the launch reads and writes in no
+ * order). k == 0 succeeds without a launch.
+ * Refusals, before any launch, with nothing written, in this order:
+ *   1 null handle; 2 no envs created; 3 a null required pointer (dst / src; ids unless k == N; in a
+ *   clone both id arrays); 4 k < 0 or k > N; 5 a buffer that is not 4-byte aligned.
+ *
+ * he_get_sim_state / he_set_sim_state: the sim-global scalars behind the per-env rows: the simulate()
+ * calls the pending wrench still acts in, whether an actuation is set, and the physics launches so far
+ * (it times the dispatch-order rebuilds only). Host only. Refusals in this order: 1 null handle; 2 no
+ * envs created; 3 null struct; then for he_set_sim_state 6 a version other than HE_STATE_VERSION or a
+ * negative wrench_hold / launches. */
+#define HE_STATE_VERSION 1
+#define HE_STATE_MAX_FIELDS 16
+typedef struct he_state_field { int32_t kind; int32_t offset_words; int32_t words; int32_t dtype; } he_state_field; /* kind -1: internal */
+typedef struct he_state_layout { uint32_t version; int32_t words; int32_t num_fields; he_state_field fields[HE_STATE_MAX_FIELDS]; } he_state_layout;
+int he_state_layout_get(he_engine* h, he_state_layout* out);
+int he_save_envs(he_engine* h, const int32_t* ids, int k, void* dst, void* stream);
+int he_load_envs(he_engine* h, const int32_t* ids, int k, const void* src, void* stream);
+int he_clone_envs(he_engine* h, const int32_t* src_ids, const int32_t* dst_ids, int k, void* stream);
+typedef struct he_sim_state { uint32_t version; int32_t wrench_hold; int32_t act_set; int64_t launches; } he_sim_state;
+int he_get_sim_state(he_engine* h, he_sim_state* out);
+int he_set_sim_state(he_engine* h, const he_sim_state* in);
+
 /* ---------------- motion library + fused imitation kernel (A5-A9) ---------------------- */
 /* MotionLibBase.load_motions table upload (motion_lib.py:396-420). Host pointers; the engine
  * re-lays the frames out as interleaved per-frame records in device memory.
