@@ -125,7 +125,7 @@ def bind_library(path, prototypes):
 
 class Library:
     """One C-ABI library of the package: where it lies, its prototype table, the prefix of its symbols
-    (``"he"``, ``"hr"``, ``"hd"``, ``"hs"``, ``"ht"``; ``"hc"``, ``"hk"``, ``"hw"`` for the second families) and the error class its binding raises. ``env``
+    (``"he"``, ``"hr"``, ``"hd"``, ``"hs"``, ``"ht"``; ``"hc"``, ``"hk"``, ``"hw"``, ``"hg"`` for the further families) and the error class its binding raises. ``env``
     names an environment variable that may point at another build (diagnostics only)."""
 
     def __init__(self, path, prototypes, prefix, error_cls, env=None):
@@ -191,7 +191,7 @@ def check_tensor(t, dtype, shape, device, what, error_cls, at_least=None):
 class QueryBinding:
     """What the bindings of the query libraries (``dynamics.Dynamics``, ``solve.Solver``,
     ``task.TaskSpace``, and the second families ``centroidal.Centroidal``, ``ik.InverseKinematics`` and
-    ``reaction.Reaction``)
+    ``reaction.Reaction``, ``derivatives.Derivatives``)
     share: an object on one engine that owns a library handle made from the engine's model and gravity, launches on the engine's stream and reads the engine's live state unless a call
     names another. A subclass states ``LIBRARY`` (its :class:`Library`) and ``NO_CPU_PATH`` (the end of
     the constructor's refusal without a device) and adds the calls that are its own."""

@@ -63,7 +63,8 @@ LIBRARIES = {lib.name: lib for lib in (
     # register algebra (he_regla.h) without being linked into it
     # no SLP vectorisation, as for the physics kernel: the elimination issues its packed FMAs itself.
     # The joint-reaction queries (include/humanoid_wrench.h, the hw_ entry points) are a second family of
-    # this library: device code in csrc/hs_wrench.h, run by torque_kernel itself
+    # this library: device code in csrc/hs_wrench.h, run by torque_kernel itself; the dynamics derivatives
+    # (include/humanoid_derivatives.h, the hg_ entry points) a third, in csrc/hs_derivs.h
     Library("solve", [("hs_solve.hip", ["-fno-slp-vectorize"])]),
     # task-space control (include/humanoid_task.h: the task Jacobian rows, J M^-1, the operational-space
     # inertia and the task solve in one launch): a fifth product library, which shares the solve kernels'
@@ -137,7 +138,8 @@ BUDGETS = {
     "hd_dynamics.hip": {"dynamics_kernel": Budget(max_scratch=0), "centroidal_kernel": Budget(max_scratch=0)},
     # the solve kernels hold the mass matrix and its factorisation in registers, within the 256 of two
     # waves per SIMD; the second query family of the translation unit (hs_wrench.h) adds no kernel: it is
-    # torque_kernel's run-time extension, staged in LDS that is dead by then
+    # torque_kernel's run-time extension, staged in LDS that is dead by then; the third (hs_derivs.h) likewise,
+    # its per-lane tangents in dynamic LDS that only its own launch asks for
     "hs_solve.hip": {"solve_kernel": Budget(max_scratch=0), "torque_kernel": Budget(max_scratch=0)},
     # the task kernel is solve_kernel's shape and declares the same two waves
     "ht_task.hip": {"task_kernel": Budget(min_waves=2, max_scratch=0)},

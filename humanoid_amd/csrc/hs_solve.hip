@@ -19,7 +19,9 @@
 //              L D L^T in every lane, tau = w - f + M_jb a_b with M_jb a_b = F_j . (a_b as a motion vector).
 //              As hw_compute launches it (include/humanoid_wrench.h, hs_wrench.h) it also takes external
 //              wrenches on the bodies and a prescribed base acceleration, and writes every joint's wrench
-//              and every body's acceleration from what it has in LDS by then.
+//              and every body's acceleration from what it has in LDS by then. As hg_compute launches it
+//              (include/humanoid_derivatives.h, hs_derivs.h) it takes the whole generalised acceleration and
+//              writes d tau / d q and d tau / d qd, a lane per direction, from its own pass through the tree.
 // Spatial quantities of a subtree are referred to its own joint origin, never to a common far point: an
 // entry of M is then exact to float32 of the descendant's own inertia (see columns()).
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@
 #include "he_regla.h"
 #include "he_topo.h"
 #include "he_tree_state.h"
+#include "hs_derivs.h"
 #include "hs_wrench.h"
 
 namespace {
@@ -58,6 +61,11 @@ struct Params {
     float* wrench;             // [N,24,6] or null
     float* body_acc;           // [N,24,6] or null
     int frame;                 // HW_FRAME_*
+    // torque_kernel as hg_compute launches it (hs_derivs.h); all null from every other entry
+    const float* acc;  // [N,75]: the generalised acceleration, or null (zero)
+    float* dtau_dq;    // [N,75,75] or null
+    float* dtau_dv;    // [N,75,75] or null
+    float* tau_full;   // [N,75] or null
 };
 
 __global__ __launch_bounds__(kWave, 2) void solve_kernel(const Params P) {
@@ -124,6 +132,11 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
     const int lane = threadIdx.x;
     const size_t env = blockIdx.x;
     const TreeModel& M = *P.model;
+    if (P.dtau_dq || P.dtau_dv || P.tau_full) {  // hg_compute: its own path through the tree, in its own LDS
+        extern __shared__ float deriv_lds[];
+        derivatives(L, M, P, deriv_lds, env, lane);
+        return;
+    }
     if (P.qdd_des) {
         columns<true>(L, M, P, env, lane);  // L.bias = w, the RNEA force at qdd = (0; qdd_des); ends on a barrier
     } else {  // hw_compute without desired accelerations: everything at qdd = 0, which columns<false> is
@@ -201,21 +214,24 @@ __global__ __launch_bounds__(kWave) void torque_kernel(const Params P) {
 
 struct hs_solver : QueryHandle<TreeModel> {};
 struct hw_reaction : QueryHandle<TreeModel> {};  // the second family's handle (include/humanoid_wrench.h)
+struct hg_derivatives : QueryHandle<TreeModel> {};  // the third family's (include/humanoid_derivatives.h)
 
 namespace {
 
 // The refusals the entry points share, in the order the headers list them, around `own`, the
 // entry point's own; then the launch. Every buffer of the call is in P; the handle is read last.
+// flags_all: the entry's flag bits; lds: the dynamic LDS its path of the kernel indexes (hs_derivs.h).
 template <class Handle, class Own>
-int launch(Handle* h, const char* who, void (*kernel)(Params), Params& P, void* stream, Own own) {
+int launch(Handle* h, const char* who, void (*kernel)(Params), Params& P, void* stream, Own own,
+           uint32_t flags_all = HS_FLAGS_ALL, size_t lds = 0) {
     if (check_call(who, h, P.root, P.dof)) return 1;
     if (own()) return 1;
-    if (check_flags(who, P.flags, HS_FLAGS_ALL)) return 1;
+    if (check_flags(who, P.flags, flags_all)) return 1;
     if (check_aligned(who, {P.root, P.dof, P.gen_force, P.qdd_des, P.rhs, P.out, P.base_acc, P.base_acc_in, P.body_force,
-                            P.body_torque, P.wrench, P.body_acc}))
+                            P.body_torque, P.wrench, P.body_acc, P.acc, P.dtau_dq, P.dtau_dv, P.tau_full}))
         return 1;
     P.model = h->d_model;
-    hipLaunchKernelGGL(kernel, dim3(h->num_envs), dim3(kWave), 0, static_cast<hipStream_t>(stream), P);
+    hipLaunchKernelGGL(kernel, dim3(h->num_envs), dim3(kWave), lds, static_cast<hipStream_t>(stream), P);
     HE_CHECK(hipGetLastError());
     return 0;
 }
@@ -327,6 +343,52 @@ int hw_compute(hw_reaction* h, const float* root_state, const float* dof_state, 
             return fail("hw_compute: frame %d outside 0..1 (HW_FRAME_WORLD, HW_FRAME_BODY)", frame);
         return 0;
     });
+}
+
+}  // extern "C"
+
+// ---- the dynamics derivatives (include/humanoid_derivatives.h, the hg_ entry points): a third family of
+// this library on torque_kernel, whose device code is hs_derivs.h
+static_assert(HG_FLAG_ARMATURE == HS_FLAG_ARMATURE && HG_FLAG_NO_GRAVITY == HS_FLAG_NO_GRAVITY &&
+                  !(HG_FLAG_BY_DIRECTION & HS_FLAGS_ALL),
+              "torque_kernel reads one set of flag bits");
+
+extern "C" {
+
+const char* hg_last_error(void) { return last_error(); }
+int hg_version(void) { return 1; }
+int hg_validate_model(const he_model* model) { return hs_validate_model(model); }
+
+int hg_create(int device, const he_model* model, const float gravity[3], int num_envs, hg_derivatives** out) {
+    return query_create("hg_create", device, model, gravity, num_envs, out, hg_validate_model, fill_tree_model);
+}
+
+int hg_destroy(hg_derivatives* h) { return query_destroy(h); }
+
+int hg_compute(hg_derivatives* h, const float* root_state, const float* dof_state, const float* acc,
+               const hg_outputs* out, uint32_t flags, void* stream) {
+    Params P{};
+    P.root = root_state;
+    P.dof = dof_state;
+    P.acc = acc;
+    P.flags = flags;
+    if (out) P.dtau_dq = out->dtau_dq, P.dtau_dv = out->dtau_dv, P.tau_full = out->tau;
+    return launch(
+        h, "hg_compute", torque_kernel, P, stream,
+        [&] {
+            if (!out) return fail("hg_compute: null output struct");
+            const float* outs[HG_NUM_OUTPUTS] = {out->dtau_dq, out->dtau_dv, out->tau};
+            if (!outs[0] && !outs[1] && !outs[2]) return fail("hg_compute: no output buffer");
+            for (int i = 0; i < HG_NUM_OUTPUTS; ++i) {
+                if (!outs[i]) continue;
+                if (outs[i] == root_state || outs[i] == dof_state || outs[i] == acc)
+                    return fail("hg_compute: an output is also an input buffer");
+                for (int j = 0; j < i; ++j)
+                    if (outs[i] == outs[j]) return fail("hg_compute: two outputs are the same buffer");
+            }
+            return 0;
+        },
+        HG_FLAGS_ALL, kDerivLds);
 }
 
 }  // extern "C"

@@ -157,6 +157,17 @@ class Dynamics(_abi.QueryBinding):
         self._reaction.armature, self._reaction.gravity = self.armature, self.gravity
         return self._reaction
 
+    @property
+    def derivatives(self):
+        """The :class:`humanoid_amd.derivatives.Derivatives` of this engine (created on first use): the
+        derivatives of the inverse and forward dynamics with respect to the pose and the generalised
+        velocity, with this object's ``armature`` and ``gravity`` settings."""
+        if getattr(self, "_derivatives", None) is None:
+            from .derivatives import Derivatives
+            self._derivatives = Derivatives(self.engine, armature=self.armature)
+        self._derivatives.armature, self._derivatives.gravity = self.armature, self.gravity
+        return self._derivatives
+
     def forward_dynamics(self, gen_force=None, out=None):
         """qdd [N,75] = M^-1 (gen_force - c) at the engine's current state: one launch, M never written."""
         return self.solver.forward_dynamics(gen_force, out)

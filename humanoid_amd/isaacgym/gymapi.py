@@ -43,6 +43,9 @@ Engine-specific behaviour (documented, not silent):
   kept in registers (``include/humanoid_solve.h``): ``solve_forward_dynamics`` (``qdd = M^-1 (f - c)``),
   ``solve_computed_torque`` (joint torques and base acceleration for desired joint accelerations) and
   ``solve_mass_matrix`` (``M^-1`` on up to 32 rows per env, e.g. a Jacobian block);
+* ENGINE EXTENSION: the derivatives of those dynamics (``include/humanoid_derivatives.h``):
+  ``solve_dynamics_derivatives`` gives d tau / d q and d tau / d qd of ``tau = M a + c`` in one launch, exact,
+  and ``solve_forward_dynamics_derivatives`` the forward dynamics with d qdd / d q, d qdd / d qd and ``M^-1``;
 * ENGINE EXTENSION: task-space control in one launch (``include/humanoid_task.h``): ``set_task_rows``
   names up to 32 task rows (velocity components of points on bodies, the same for every env), and
   ``solve_task_space`` gives the generalised force (``mode="force"``: ``J^T F``) or the joint torques
@@ -584,6 +587,36 @@ class Gym:
         """Engine extension: out [N,k,75] = M^-1 on each of the k <= 32 rows of rhs [N,k,75]."""
         dyn = self._solve_dynamics(sim, "solve_mass_matrix")
         dyn.solve(self._tensor(rhs_desc), self._tensor(out_desc))
+        return True
+
+    def solve_dynamics_derivatives(self, sim: Sim, acc_desc, dtau_dq_out_desc=None, dtau_dv_out_desc=None,
+                                   tau_out_desc=None, by_direction=False):
+        """Engine extension: the derivatives of the inverse dynamics tau = M a + c at the current state and
+        the generalised acceleration acc [N,75] (None: zero), in one launch
+        (``include/humanoid_derivatives.h``): dtau_dq [N,75,75] along the pose directions, dtau_dv [N,75,75]
+        with respect to the generalised velocity, both indexed [i, j] (``by_direction``: [j, i]), and tau
+        [N,75] itself. An output whose descriptor is None is not computed; at least one must be given."""
+        dyn = self._solve_dynamics(sim, "solve_dynamics_derivatives")
+        out = {name: self._tensor(d) for name, d in (("dtau_dq", dtau_dq_out_desc), ("dtau_dv", dtau_dv_out_desc),
+                                                     ("tau", tau_out_desc)) if d is not None}
+        dyn.derivatives.inverse_dynamics(None if acc_desc is None else self._tensor(acc_desc), dtau_dq=False,
+                                         dtau_dv=False, by_direction=by_direction, out=out)
+        return True
+
+    def solve_forward_dynamics_derivatives(self, sim: Sim, gen_force_desc, qdd_out_desc, dqdd_dq_out_desc,
+                                           dqdd_dv_out_desc, dqdd_dtau_out_desc=None):
+        """Engine extension: the forward dynamics qdd [N,75] = M^-1 (gen_force - c) at the current state
+        (``gen_force_desc`` [N,75] or None for zero) with its derivatives along the pose directions and with
+        respect to the generalised velocity, [N,75,75] each indexed [i, j], and M^-1 [N,75,75] when
+        ``dqdd_dtau_out_desc`` is given: what a linearisation x' = A x + B u of the continuous dynamics
+        is assembled from."""
+        dyn = self._solve_dynamics(sim, "solve_forward_dynamics_derivatives")
+        r = dyn.derivatives.forward_dynamics(None if gen_force_desc is None else self._tensor(gen_force_desc),
+                                             dqdd_dtau=dqdd_dtau_out_desc is not None)
+        for name, d in (("qdd", qdd_out_desc), ("dqdd_dq", dqdd_dq_out_desc), ("dqdd_dv", dqdd_dv_out_desc),
+                        ("dqdd_dtau", dqdd_dtau_out_desc)):
+            if d is not None:
+                self._tensor(d).copy_(r[name])
         return True
 
     # -- task-space control (engine extensions) -----------------------------------------------------
