@@ -18,7 +18,6 @@ compared once before timing. The fused launch's bytes written over its time are 
 
     python tools/centroidal_bench.py [--out profiles/centroidal/centroidal_bench.json]
 """
-import argparse
 import json
 import os
 import statistics
@@ -26,11 +25,10 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from dynamics_bench import random_state  # noqa: E402
+import bench_common as bc  # noqa: E402
+from bench_common import NB, ND  # noqa: E402
 
 HBM_PEAK_TBS = 8.0        # HBM3E, specification
 HBM_ACHIEVABLE_TBS = 6.3  # measured with a float4 copy
@@ -39,46 +37,25 @@ CASES = {"all_six": ("com", "com_vel", "momentum", "cmm", "cmm_bias", "energy"),
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "centroidal", "centroidal_bench.json"))
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
-    args = ap.parse_args()
+    args = bc.parser("profiles/centroidal/centroidal_bench.json").parse_args()
     import torch
-    from humanoid_amd import build
     from humanoid_amd import dynamics as D
     from humanoid_amd.centroidal import OUTPUTS, output_shapes
-    from humanoid_amd.engine import Engine
     from humanoid_amd.model import load_default_model
     n = args.envs
-    model = load_default_model()
-    eng = Engine(model, n, device=0)
-    dev = eng.device
-    root, dof = random_state(n, np.random.default_rng(0))
+    root, dof = bc.random_state(n, np.random.default_rng(0))
     root[:, 2] += 3.0  # in the air: the one simulate call below meets no ground
-    ids = torch.arange(n, dtype=torch.int32, device=dev)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(dev), ids)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * 69, 2)).to(dev), ids)
-    eng.simulate(1)  # the rigid-body tensor now belongs to the root and dof state
+    eng = bc.seeded_engine(n, root, dof, simulate=1)  # the rigid-body tensor now belongs to the root and dof state
+    dev = eng.device
     dyn = D.Dynamics(eng, armature=False)
     dyn.gravity = False
     cen = dyn.centroidal
+    model = load_default_model()
     mass = torch.tensor(np.asarray(model.mass, np.float32), device=dev)
     lcom = torch.tensor(np.asarray(model.com, np.float32), device=dev)
     mtot = mass.sum()
     g = torch.tensor([float(x) for x in eng.params.gravity], device=dev)
-    rb = eng.rb_state.view(n, 24, 13)
-
-    def timed(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / args.calls
+    rb = eng.rb_state.view(n, NB, 13)
 
     def shifted(rows, r):  # [N,6,k]: the angular rows less r x the linear rows
         return torch.cat([rows[:, 0:3], rows[:, 3:6] - torch.cross(r.unsqueeze(-1).expand_as(rows[:, 0:3]), rows[:, 0:3], dim=1)],
@@ -96,7 +73,7 @@ def main():
         def recipe():
             dyn.refresh(jacobian=False, bias=full)
             q, u = rb[:, :, 3:6], rb[:, :, 6:7]
-            t = 2.0 * torch.cross(q, lcom.expand(n, 24, 3), dim=2)
+            t = 2.0 * torch.cross(q, lcom.expand(n, NB, 3), dim=2)
             cb = rb[:, :, 0:3] + lcom + u * t + torch.cross(q, t, dim=2)
             com = (mass[None, :, None] * cb).sum(1) / mtot
             r = com - eng.root_states[:, 0:3]
@@ -111,41 +88,27 @@ def main():
                 out["energy"] = torch.stack([kin, -mtot * (com @ g)], dim=1)
             return out
 
-        for _ in range(args.warmup):
-            a, b = fused(), recipe()
-        torch.cuda.synchronize()
-        diff = {k: float((a[k] - b[k]).abs().max()) for k in names}
-        tk, tr = [], []
-        for _ in range(args.blocks):
-            tk.append(timed(fused))
-            tr.append(timed(recipe))
-        mk, mr = statistics.median(tk), statistics.median(tr)
+        t, diff = bc.alternate(dict(fused=fused, recipe=recipe), args.warmup, args.calls, args.blocks, lambda o: {
+            k: float((o["fused"][k] - o["recipe"][k]).abs().max()) for k in names})
+        tk, tr = t["fused"], t["recipe"]
+        mk = statistics.median(tk)
         shapes = output_shapes(n)
         written = 4 * sum(int(np.prod(shapes[k])) for k in names)
-        read = 4 * n * (13 + 69 * 2)
-        results.append(dict(case=case, outputs=list(names), fused_ms=round(mk, 5), fused_blocks_ms=[round(t, 5) for t in tk],
-                            recipe_ms=round(mr, 5), recipe_blocks_ms=[round(t, 5) for t in tr],
-                            recipe_over_fused=round(mr / mk, 2),
-                            slowest_fused_over_fastest_recipe=round(max(tk) / min(tr), 4),
+        read = 4 * n * (13 + ND * 2)
+        results.append(dict(case=case, outputs=list(names), **bc.side_fields("fused", tk), **bc.side_fields("recipe", tr),
+                            recipe_over_fused=bc.over(tr, tk, 2),
+                            slowest_fused_over_fastest_recipe=bc.slowest_over_fastest(tk, tr),
                             max_abs_difference=diff, bytes_written=written, bytes_read=read,
                             written_tb_per_s=round(written / (mk * 1e-3) / 1e12, 4),
                             fraction_of_hbm_peak=round(written / (mk * 1e-3) / 1e12 / HBM_PEAK_TBS, 4)))
         print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/centroidal_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               calls_per_block=args.calls, blocks=args.blocks,
-               recipe="Dynamics.refresh(jacobian=False), armature and gravity off; the centre of mass from the rigid-body "
-                      "tensor; torch for the re-referencing, A_G qd and the energies",
-               timing="HIP events around each block of calls, host launch cost included on both sides",
-               hbm_peak_tb_per_s=HBM_PEAK_TBS, hbm_achievable_tb_per_s=HBM_ACHIEVABLE_TBS,
-               bound="one wave per env runs a serial tree pass of 8 levels before it stores 1.9 KB: the launch is "
-                     "bound by that latency and by the launch itself, not by HBM (see fraction_of_hbm_peak)",
-               dynamics_library_device_code_id=build.device_code_id(build.LIBRARIES["dynamics"].path),
-               engine_device_code_id=build.device_code_id(build.LIB), results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/centroidal_bench.py", args, ["dynamics", "engine"], results,
+                    recipe="Dynamics.refresh(jacobian=False), armature and gravity off; the centre of mass from the "
+                           "rigid-body tensor; torch for the re-referencing, A_G qd and the energies",
+                    timing="HIP events around each block of calls, host launch cost included on both sides",
+                    hbm_peak_tb_per_s=HBM_PEAK_TBS, hbm_achievable_tb_per_s=HBM_ACHIEVABLE_TBS,
+                    bound="one wave per env runs a serial tree pass of 8 levels before it stores 1.9 KB: the launch is "
+                          "bound by that latency and by the launch itself, not by HBM (see fraction_of_hbm_peak)")
 
 
 if __name__ == "__main__":

@@ -37,63 +37,17 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_common as bc  # noqa: E402
+from bench_common import NB, ND, NG, ROOT, quat_exp, quat_mul, quat_rotvec  # noqa: E402
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from dynamics_bench import random_state  # noqa: E402
-
-NB, ND, NG = 24, 69, 75
 H_Q, H_V = 5e-3, 1.0  # float32 steps: (3 eps)^(1/3) of an angle of order 1; tau is quadratic in qd
 
 
-def engine_with(n, root, dof):
-    import torch
-    from humanoid_amd.engine import Engine
-    from humanoid_amd.model import load_default_model
-    eng = Engine(load_default_model(), n, device=0)
-    ids = torch.arange(n, dtype=torch.int32, device=eng.device)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(eng.device), ids)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * ND, 2)).to(eng.device), ids)
-    return eng
-
-
-def timed(fn, calls):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(calls):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / calls
-
-
 # ------------------------------------------------------------------ the replaced path's pose arithmetic
-def quat_mul(a, b):
-    import torch
-    ax, ay, az, aw = a.unbind(-1)
-    bx, by, bz, bw = b.unbind(-1)
-    return torch.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
-                        aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], -1)
-
-
-def quat_exp(v):
-    import torch
-    th = v.norm(dim=-1, keepdim=True)
-    s = torch.where(th < 1e-3, 0.5 - th * th / 48, torch.sin(0.5 * th) / th.clamp_min(1e-12))
-    return torch.cat([v * s, torch.cos(0.5 * th)], -1)
-
-
-def quat_rotvec(q):
-    import torch
-    q = torch.where(q[..., 3:] < 0, -q, q)
-    sn = q[..., :3].norm(dim=-1, keepdim=True)
-    f = torch.where(sn < 5e-4, 2.0 / q[..., 3:], 2.0 * torch.atan2(sn, q[..., 3:]) / sn.clamp_min(1e-12))
-    return q[..., :3] * f
-
-
 def moved_states(root, dof, j, h):
     """(root', dof') at q (+) h e_j: torch float32, batched over the envs."""
     import torch
@@ -136,18 +90,15 @@ def differences(fun, root, dof, pose, out):
 def bench(args):
     import torch
     import derivative_reference as GR
-    from humanoid_amd import build
     from humanoid_amd.derivatives import Derivatives
     from humanoid_amd.reaction import Reaction
     from humanoid_amd.solve import Solver
     n = args.envs
-    root_h, dof_h = random_state(n, np.random.default_rng(0))
-    eng = engine_with(n, root_h, dof_h)
+    eng = bc.seeded_engine(n, *bc.random_state(n, np.random.default_rng(0)))
     dev = eng.device
     dv, rx, sol = Derivatives(eng), Reaction(eng), Solver(eng)
     gen = torch.Generator(device=dev).manual_seed(1)
-    acc = (torch.rand(n, NG, device=dev, generator=gen) * 2 - 1) * 20.0
-    f = (torch.rand(n, NG, device=dev, generator=gen) * 2 - 1) * 50.0
+    acc, f = bc.uniform((n, NG), 20.0, gen), bc.uniform((n, NG), 50.0, gen)
     root, dof = eng.root_states.clone(), eng.dof_state.clone()
     base_acc, qdd_des = acc[:, :6].contiguous(), acc[:, 6:].contiguous()
     f32 = dict(dtype=torch.float32, device=dev)
@@ -201,36 +152,21 @@ def bench(args):
 
     results = []
     for name, kern, rep in cases:
-        for _ in range(args.warmup):
-            kern()
-        rep()
-        torch.cuda.synchronize()
-        tk, tr = [], []
-        for _ in range(args.blocks):
-            tk.append(timed(kern, args.calls))
-            tr.append(timed(rep, args.replaced_calls))
-        mk, mr = statistics.median(tk), statistics.median(tr)
-        results.append(dict(case=name, kernel_ms=round(mk, 5), kernel_blocks_ms=[round(t, 5) for t in tk],
-                            replaced_ms=round(mr, 3), replaced_blocks_ms=[round(t, 3) for t in tr],
-                            replaced_over_kernel=round(mr / mk, 1)))
+        t = bc.alternate(dict(kernel=kern, replaced=rep), dict(kernel=args.warmup, replaced=1),
+                         dict(kernel=args.calls, replaced=args.replaced_calls), args.blocks)[0]
+        results.append(dict(case=name, **bc.side_fields("kernel", t["kernel"]), **bc.side_fields("replaced", t["replaced"], 3),
+                            replaced_over_kernel=bc.over(t["replaced"], t["kernel"], 1)))
         print(json.dumps(results[-1]), flush=True)
-    t_ct = statistics.median(timed(lambda: sol.computed_torque(qdd_des, None, hw["tau"], ab_buf), args.calls)
+    t_ct = statistics.median(bc.timed(lambda: sol.computed_torque(qdd_des, None, hw["tau"], ab_buf), args.calls)
                              for _ in range(args.blocks))
-    t_hw = statistics.median(timed(lambda: tau_by_launch(root, dof), args.calls) for _ in range(args.blocks))
-    rec = dict(tool="tools/derivatives_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               calls_per_block=args.calls, replaced_calls_per_block=args.replaced_calls, blocks=args.blocks,
-               replaced="central differences in float32 (pose step %g, velocity step %g) through torque_kernel launches "
-                        "(hw_compute, prescribed base: all 75 rows) on states perturbed in torch, 2 x 72 + 2 x 75 "
-                        "launches for both matrices; the forward form through hs_forward_dynamics likewise" % (H_Q, H_V),
-               one_launch_ms=dict(hs_computed_torque=round(t_ct, 5), hw_compute_with_the_torch_concatenation=round(t_hw, 5)),
-               check_envs=m, errors_against_float64=errors,
-               solve_library_device_code_id=build.device_code_id(build.LIBRARIES["solve"].path),
-               engine_device_code_id=build.device_code_id(build.LIB), results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    t_hw = statistics.median(bc.timed(lambda: tau_by_launch(root, dof), args.calls) for _ in range(args.blocks))
+    bc.write_record(args.out, "tools/derivatives_bench.py", args, ["solve", "engine"], results,
+                    replaced="central differences in float32 (pose step %g, velocity step %g) through torque_kernel launches "
+                             "(hw_compute, prescribed base: all 75 rows) on states perturbed in torch, 2 x 72 + 2 x 75 "
+                             "launches for both matrices; the forward form through hs_forward_dynamics likewise" % (H_Q, H_V),
+                    one_launch_ms=dict(hs_computed_torque=round(t_ct, 5),
+                                       hw_compute_with_the_torch_concatenation=round(t_hw, 5)),
+                    check_envs=m, errors_against_float64=errors)
     del dv, rx, sol, eng
     return 0
 
@@ -250,12 +186,11 @@ def ab_side(args):
         n = root_h.shape[0]
     else:
         n = args.envs
-        root_h, dof_h = random_state(n, np.random.default_rng(0))
-    eng = engine_with(n, root_h, dof_h)
-    dev = eng.device
+        root_h, dof_h = bc.random_state(n, np.random.default_rng(0))
+    eng = bc.seeded_engine(n, root_h, dof_h)
     sol, rx = solve.Solver(eng), reaction.Reaction(eng)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    rand = lambda shape, s: (torch.rand(shape, device=dev, generator=gen) * 2 - 1) * s  # noqa: E731
+    gen = torch.Generator(device=eng.device).manual_seed(1)
+    rand = lambda shape, s: bc.uniform(shape, s, gen)  # noqa: E731
     f, qdd_des, base_acc = rand((n, NG), 100.0), rand((n, ND), 20.0), rand((n, 6), 10.0)
     force, torque, rhs = rand((n * NB, 3), 200.0), rand((n * NB, 3), 20.0), rand((n, 6, NG), 1.0)
     entries = {
@@ -283,7 +218,7 @@ def ab_side(args):
             for _ in range(args.warmup):
                 fn()
             torch.cuda.synchronize()
-            res[name] = [timed(fn, args.calls) for _ in range(args.blocks)]
+            res[name] = [bc.timed(fn, args.calls) for _ in range(args.blocks)]
         print("AB_SIDE " + json.dumps(res), flush=True)
     del sol, rx, eng
     return 0
@@ -338,22 +273,13 @@ def ab(args):
                calls_per_block=args.calls, blocks=args.blocks, passes=args.passes,
                new_solve_library_device_code_id=ids["new"], parent_solve_library_device_code_id=ids["parent"],
                outputs_identical=not differs, results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    bc.dump(args.out, rec)
     return 1 if differs else 0
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20)
+    ap = bc.parser(None)
     ap.add_argument("--replaced-calls", type=int, default=1)
-    ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--check-envs", type=int, default=8)
     ap.add_argument("--ab", metavar="PARENT_DIR", help="a directory with the parent commit's libhumanoid_solve.so")
     ap.add_argument("--passes", type=int, default=3)

@@ -10,7 +10,6 @@ dword per lane, 256 B per wave instruction (6.0-6.2 TB/s; 6.0 is used).
 
     python tools/dynamics_bench.py [--out profiles/r09/dynamics_bench.json]
 """
-import argparse
 import json
 import os
 import statistics
@@ -18,44 +17,21 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_common as bc  # noqa: E402
 
 STORE_RATE = 6.0e12  # B/s
 
 
-def random_state(n, rng):
-    root = np.zeros((n, 13), np.float32)
-    root[:, :2] = rng.uniform(-1, 1, (n, 2))
-    root[:, 2] = rng.uniform(0.9, 1.6, n)
-    q = rng.normal(size=(n, 4))
-    root[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
-    root[:, 7:13] = rng.normal(0, 1.0, (n, 6))
-    dof = np.zeros((n, 69, 2), np.float32)
-    dof[..., 0] = rng.uniform(-0.6, 0.6, (n, 69))
-    dof[..., 1] = rng.normal(0, 1.0, (n, 69))
-    return root, dof
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "dynamics_bench.json"))
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap = bc.parser("profiles/r09/dynamics_bench.json", warmup=20, calls=None, blocks=None)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
-    import torch
-    from humanoid_amd import build
     from humanoid_amd import dynamics as D
-    from humanoid_amd.engine import Engine
-    from humanoid_amd.model import load_default_model
     n = args.envs
-    eng = Engine(load_default_model(), n, device=0)
-    root, dof = random_state(n, np.random.default_rng(0))
-    ids = torch.arange(n, dtype=torch.int32, device=eng.device)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(eng.device), ids)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * 69, 2)).to(eng.device), ids)
+    eng = bc.seeded_engine(n, *bc.random_state(n, np.random.default_rng(0)))
     dyn = D.Dynamics(eng)
     nbytes = {k: 4 * int(np.prod(s)) for k, s in D.output_shapes(n).items()}
     cases = (("all", ("jacobian", "mass_matrix", "bias")), ("jacobian", ("jacobian",)),
@@ -65,15 +41,7 @@ def main():
         kw = {k: k in outs for k in ("jacobian", "mass_matrix", "bias")}
         for _ in range(args.warmup):
             dyn.refresh(**kw)
-        times = []
-        for _ in range(args.repeats):
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(args.launches):
-                dyn.refresh(**kw)
-            t1.record()
-            torch.cuda.synchronize()
-            times.append(t0.elapsed_time(t1) / args.launches)
+        times = [bc.timed(lambda: dyn.refresh(**kw), args.launches) for _ in range(args.repeats)]
         ms = statistics.median(times)
         written = sum(nbytes[k] for k in outs)
         rate = written / (ms * 1e-3)
@@ -82,14 +50,8 @@ def main():
                             store_floor_ms=round(written / STORE_RATE * 1e3, 5), tb_per_s=round(rate / 1e12, 3),
                             fraction_of_store_rate=round(rate / STORE_RATE, 3)))
         print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/dynamics_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               launches=args.launches, repeats=args.repeats, store_rate_tb_per_s=STORE_RATE / 1e12,
-               dynamics_library_device_code_id=build.device_code_id(build.LIBRARIES["dynamics"].path), results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(rec, f, indent=1)
-        f.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/dynamics_bench.py", args, ["dynamics"], results,
+                    store_rate_tb_per_s=STORE_RATE / 1e12)
 
 
 if __name__ == "__main__":

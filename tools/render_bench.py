@@ -17,23 +17,24 @@ one's, alternately, in processes of their own); cases whose entry points that bu
 
     python tools/render_bench.py [--out profiles/r08/render_bench.json] [--cases all] [--lib PATH]
 """
-import argparse
 import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_common as bc  # noqa: E402
+from bench_common import NB, ROOT  # noqa: E402
 
 
 def standing_pose(model, n, rng):
     """rb_state [n,24,13]: the rest pose (identity rotations, joint offsets summed down the tree) at
     z = 0.89 with a sub-metre xy jitter."""
-    rb = np.zeros((n, 24, 13), np.float32)
-    pos = np.zeros((24, 3))
-    for b in range(24):
+    rb = np.zeros((n, NB, 13), np.float32)
+    pos = np.zeros((NB, 3))
+    for b in range(NB):
         p = int(model.parents[b])
         pos[b] = (pos[p] if p >= 0 else np.array([0.0, 0.0, 0.89])) + (model.local_pos[b] if p >= 0 else 0.0)
     rb[:, :, :3] = pos[None] + np.concatenate([rng.uniform(-1, 1, (n, 1, 2)), np.zeros((n, 1, 1))], -1)
@@ -41,30 +42,13 @@ def standing_pose(model, n, rng):
     return rb
 
 
-def timed(fn, warmup, launches):
-    """ms per call: HIP events around `launches` calls after `warmup` calls."""
-    import torch
-    for _ in range(warmup):
-        fn()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(launches):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / launches
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "render_bench.json"))
-    ap.add_argument("--warmup", type=int, default=20)
+    ap = bc.parser("profiles/r08/render_bench.json", envs=None, warmup=20, calls=None, blocks=None)
     ap.add_argument("--launches", type=int, default=100)
     ap.add_argument("--cases", default="all", choices=("all", "plane", "terrain", "rays"))
     ap.add_argument("--lib", default=None, help="another build of libhumanoid_render.so to time")
     args = ap.parse_args()
     import torch
-    from humanoid_amd import build
     from humanoid_amd import render as R
     from humanoid_amd.engine import Engine
     from humanoid_amd.model import load_default_model
@@ -75,14 +59,20 @@ def main():
         R.load_library(args.lib)
     has_new = "hr_set_terrain" in R._LIBRARY.prototypes
     want = lambda group: args.cases in ("all", group) and (group == "plane" or has_new)  # noqa: E731
+
+    def launch_ms(fn):  # ms per call: HIP events around `launches` calls after `warmup` calls
+        for _ in range(args.warmup):
+            fn()
+        return bc.timed(fn, args.launches)
+
     model = load_default_model()
     n = 64
     eng = Engine(model, n, device=0)
     rng = np.random.default_rng(0)
     rb = standing_pose(model, n, rng)
-    eng.rb_state.view(n, 24, 13).copy_(torch.from_numpy(rb).to(eng.device))
+    eng.rb_state.view(n, NB, 13).copy_(torch.from_numpy(rb).to(eng.device))
     ren = R.Renderer(eng)
-    mpos = torch.from_numpy(rb[:, :, :3] + rng.normal(0, 0.08, (n, 24, 3)).astype(np.float32)).to(eng.device).contiguous()
+    mpos = torch.from_numpy(rb[:, :, :3] + rng.normal(0, 0.08, (n, NB, 3)).astype(np.float32)).to(eng.device).contiguous()
     ren.set_markers(mpos, (0.8, 0.0, 0.0), 0.05)
     results = []
     for name, k, w, h in (("1x1600x900", 1, 1600, 900), ("64x320x180", 64, 320, 180)):
@@ -97,8 +87,8 @@ def main():
                 if not want("plane"):
                     continue
                 flags = R.FLAG_CHECKER | (R.FLAG_SHADOWS if shadows else 0) | (0 if cull else R.FLAG_NO_CULL)
-                ms = timed(lambda: ren.render(flags), args.warmup, args.launches)
-                tests = pixels * 48 + (hit * 24 if shadows else 0)
+                ms = launch_ms(lambda: ren.render(flags))
+                tests = pixels * 48 + (hit * NB if shadows else 0)
                 results.append(dict(case=name, cameras=k, width=w, height=h, shadows=shadows, culling=cull,
                                     ms_per_render=round(ms, 5), pixels=pixels, pixels_hit=hit,
                                     primitive_tests_unculled=tests,
@@ -111,7 +101,7 @@ def main():
             ren.render(R.FLAGS_DEFAULT)
             torch.cuda.synchronize()
             hit_t = int(torch.isfinite(ren.depth).sum())
-            ms = timed(lambda: ren.render(R.FLAGS_DEFAULT), args.warmup, args.launches)
+            ms = launch_ms(lambda: ren.render(R.FLAGS_DEFAULT))
             results.append(dict(case=name + "-steps", cameras=k, width=w, height=h, shadows=True, culling=True,
                                 terrain="steps", step_height=par.step_height, step_length=par.step_length,
                                 ms_per_render=round(ms, 5), pixels=pixels, pixels_hit=hit_t))
@@ -120,27 +110,21 @@ def main():
     if want("rays"):  # a height scan under each of 4096 standing humanoids, half of them on the steps
         big, grid = 4096, 11
         eng_r = Engine(model, big, device=0)
-        eng_r.rb_state.view(big, 24, 13).copy_(torch.from_numpy(standing_pose(model, big, rng)).to(eng_r.device))
+        eng_r.rb_state.view(big, NB, 13).copy_(torch.from_numpy(standing_pose(model, big, rng)).to(eng_r.device))
         scan = R.Renderer(eng_r)
         kind = (torch.arange(big, device=eng_r.device) % 2 * 2).to(torch.int32)
         scan.set_terrain(kind, eng_r.params.terrain_slope, eng_r.params.step_height, eng_r.params.step_length)
         scan.set_rays(R.height_scan_rays(grid, grid, 0.1, 1.0), body="Pelvis", frame="heading")
         for skip in (True, False):
-            ms = timed(lambda: scan.cast_rays(10.0, skip_bodies=skip), args.warmup, args.launches)
+            ms = launch_ms(lambda: scan.cast_rays(10.0, skip_bodies=skip))
             rays = big * grid * grid
             results.append(dict(case=f"rays-{big}x{grid * grid}", envs=big, rays_per_env=grid * grid, skip_bodies=skip,
                                 ms_per_cast=round(ms, 5), grays_per_s=round(rays / ms / 1e6, 3),
                                 rays_hit=int(torch.isfinite(scan.ray_dist).sum())))
             print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/render_bench.py", device=torch.cuda.get_device_name(0), warmup=args.warmup,
-               launches=args.launches, envs=n, primitives_per_env=48, cases=args.cases,
-               render_library=os.path.relpath(args.lib, ROOT) if args.lib else "humanoid_amd/libhumanoid_render.so",
-               render_library_device_code_id=build.device_code_id(args.lib or build.LIBRARIES["render"].path), results=results)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(rec, f, indent=1)
-        f.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/render_bench.py", args, {"render": args.lib}, results, envs=n, primitives_per_env=48,
+                    cases=args.cases,
+                    render_library=os.path.relpath(args.lib, ROOT) if args.lib else "humanoid_amd/libhumanoid_render.so")
 
 
 if __name__ == "__main__":

@@ -12,52 +12,37 @@ every velocity nonzero). The two sides' outputs are compared once before timing.
 
     python tools/solve_bench.py [--out profiles/r12/solve_cost.json]
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from dynamics_bench import random_state  # noqa: E402
+import bench_common as bc  # noqa: E402
+from bench_common import ND, NG  # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "solve_cost.json"))
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = bc.parser("profiles/r12/solve_cost.json")
     ap.add_argument("--body", type=int, default=23, help="the body whose Jacobian block is solve_k6's rhs (23: R_Hand)")
     args = ap.parse_args()
     import torch
-    from humanoid_amd import build
     from humanoid_amd import dynamics as D
-    from humanoid_amd.engine import Engine
-    from humanoid_amd.model import load_default_model
     from humanoid_amd.solve import Solver
     n = args.envs
-    eng = Engine(load_default_model(), n, device=0)
+    eng = bc.seeded_engine(n, *bc.random_state(n, np.random.default_rng(0)))
     dev = eng.device
-    root, dof = random_state(n, np.random.default_rng(0))
-    ids = torch.arange(n, dtype=torch.int32, device=dev)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(dev), ids)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * 69, 2)).to(dev), ids)
     dyn, sol = D.Dynamics(eng), Solver(eng)
     gen = torch.Generator(device=dev).manual_seed(1)
-    f = torch.zeros(n, 75, device=dev)
-    f[:, 6:] = (torch.rand(n, 69, device=dev, generator=gen) * 2 - 1) * 100.0
-    qdd_des = (torch.rand(n, 69, device=dev, generator=gen) * 2 - 1) * 20.0
+    f = torch.zeros(n, NG, device=dev)
+    f[:, 6:] = bc.uniform((n, ND), 100.0, gen)
+    qdd_des = bc.uniform((n, ND), 20.0, gen)
     dyn.refresh()
     J = dyn.jacobian[:, args.body].contiguous()  # [N,6,75]
-    out_q, out_t, out_a, out_x = (torch.empty(n, 75, device=dev), torch.empty(n, 69, device=dev),
-                                  torch.empty(n, 6, device=dev), torch.empty(n, 6, 75, device=dev))
+    out_q, out_t, out_a, out_x = (torch.empty(n, NG, device=dev), torch.empty(n, ND, device=dev),
+                                  torch.empty(n, 6, device=dev), torch.empty(n, 6, NG, device=dev))
     M, c = dyn.mass_matrix, dyn.bias
 
     def fd_kernel():
@@ -83,41 +68,17 @@ def main():
         dyn.refresh()
         return torch.linalg.solve(M, dyn.jacobian[:, args.body].transpose(1, 2)).transpose(1, 2)
 
-    def timed(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / args.calls
-
     results = []
     for name, kern, ref in (("forward_dynamics", fd_kernel, fd_torch), ("computed_torque", ct_kernel, ct_torch),
                             ("solve_k6", k6_kernel, k6_torch)):
-        for _ in range(args.warmup):
-            a, b = kern(), ref()
-        torch.cuda.synchronize()
-        diff = float((a - b).abs().max() / b.abs().max())
-        tk, tr = [], []
-        for _ in range(args.blocks):
-            tk.append(timed(kern))
-            tr.append(timed(ref))
-        mk, mr = statistics.median(tk), statistics.median(tr)
-        results.append(dict(case=name, kernel_ms=round(mk, 5), kernel_blocks_ms=[round(t, 5) for t in tk],
-                            replaced_ms=round(mr, 5), replaced_blocks_ms=[round(t, 5) for t in tr],
-                            speedup=round(mr / mk, 1), slowest_kernel_over_fastest_replaced=round(max(tk) / min(tr), 4),
+        t, diff = bc.alternate(dict(kernel=kern, replaced=ref), args.warmup, args.calls, args.blocks, lambda o: float(
+            (o["kernel"] - o["replaced"]).abs().max() / o["replaced"].abs().max()))
+        tk, tr = t["kernel"], t["replaced"]
+        results.append(dict(case=name, **bc.side_fields("kernel", tk), **bc.side_fields("replaced", tr),
+                            speedup=bc.over(tr, tk, 1), slowest_kernel_over_fastest_replaced=bc.slowest_over_fastest(tk, tr),
                             max_abs_difference_over_max=diff))
         print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/solve_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               calls_per_block=args.calls, blocks=args.blocks, body=args.body,
-               solve_library_device_code_id=build.device_code_id(build.LIBRARIES["solve"].path),
-               engine_device_code_id=build.device_code_id(build.LIB), results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/solve_bench.py", args, ["solve", "engine"], results, body=args.body)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ spread per side. The two sides' results are compared once before timing.
 
     python tools/state_bench.py [--out profiles/state/state_bench.json]
 """
-import argparse
 import json
 import os
 import statistics
@@ -25,11 +24,9 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from dynamics_bench import random_state  # noqa: E402
+import bench_common as bc  # noqa: E402
 
 PUBLIC = ("root_states", "dof_state", "rb_state", "contact_forces", "dof_force", "dof_targets", "num_contacts",
           "dropped_contacts", "contact_cache", "initial_root_states")
@@ -37,25 +34,12 @@ FIELDS = ("root", "dof_state", "rb", "cf", "dof_force", "targets", "num_contacts
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "state", "state_bench.json"))
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
-    args = ap.parse_args()
+    args = bc.parser("profiles/state/state_bench.json").parse_args()
     import torch
-    from humanoid_amd import build
-    from humanoid_amd.engine import Engine
-    from humanoid_amd.model import load_default_model
     n = args.envs
-    eng = Engine(load_default_model(), n, device=0)
+    # simulate(2): contacts, a warm-start cache, forces: every field holds something
+    eng = bc.seeded_engine(n, *bc.random_state(n, np.random.default_rng(0)), simulate=2)
     dev = eng.device
-    root, dof = random_state(n, np.random.default_rng(0))
-    every = torch.arange(n, dtype=torch.int32, device=dev)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(dev), every)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * 69, 2)).to(dev), every)
-    eng.simulate(2)  # contacts, a warm-start cache, forces: every field holds something
     words = eng.state_layout[0]
     rows = [getattr(eng, name).view(n, -1) for name in PUBLIC]  # zero-copy [N, words of the buffer]
     replaced_words = sum(r.shape[1] for r in rows)
@@ -88,47 +72,21 @@ def main():
     for f, r in zip(FIELDS, part_rows):
         assert torch.equal(eng.state_field(part, f), r), f
 
-    def timed(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / args.calls
-
     results = []
     for name, k, kern, ref in cases:
-        for _ in range(args.warmup):
-            kern()
-            ref()
-        torch.cuda.synchronize()
-        tk, tr = [], []
-        for _ in range(args.blocks):
-            tk.append(timed(kern))
-            tr.append(timed(ref))
-        mk, mr = statistics.median(tk), statistics.median(tr)
+        t = bc.alternate(dict(kernel=kern, replaced=ref), args.warmup, args.calls, args.blocks)[0]
+        tk, tr = t["kernel"], t["replaced"]
         moved = 2 * k * words * 4
-        results.append(dict(case=name, k=k, kernel_ms=round(mk, 5), kernel_blocks_ms=[round(t, 5) for t in tk],
-                            kernel_bytes=moved, kernel_effective_gb_per_s=round(moved / (mk * 1e-3) / 1e9, 1),
-                            replaced_ms=round(mr, 5), replaced_blocks_ms=[round(t, 5) for t in tr],
-                            replaced_over_kernel=round(mr / mk, 2),
-                            slowest_kernel_over_fastest_replaced=round(max(tk) / min(tr), 4)))
+        results.append(dict(case=name, k=k, **bc.side_fields("kernel", tk), kernel_bytes=moved,
+                            kernel_effective_gb_per_s=round(moved / (statistics.median(tk) * 1e-3) / 1e9, 1),
+                            **bc.side_fields("replaced", tr), replaced_over_kernel=bc.over(tr, tk, 2),
+                            slowest_kernel_over_fastest_replaced=bc.slowest_over_fastest(tk, tr)))
         print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/state_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               calls_per_block=args.calls, blocks=args.blocks, words_per_env=words,
-               replaced_words_per_env=replaced_words,
-               note="the replaced path is one indexing op per public buffer; it cannot reach the internal rows (pending "
-                    "wrench, actuation), so it moves replaced_words_per_env of words_per_env words per env and cannot "
-                    "restore an env; times include the host's launch work (20 back-to-back calls between two events)",
-               engine_device_code_id=build.device_code_id(build.LIB),
-               engine_phases_device_code_id=build.device_code_id(build.LIBRARIES["engine_phases"].path),
-               results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/state_bench.py", args, ["engine", "engine_phases"], results, words_per_env=words,
+                    replaced_words_per_env=replaced_words,
+                    note="the replaced path is one indexing op per public buffer; it cannot reach the internal rows (pending "
+                         "wrench, actuation), so it moves replaced_words_per_env of words_per_env words per env and cannot "
+                         "restore an env; times include the host's launch work (20 back-to-back calls between two events)")
 
 
 if __name__ == "__main__":

@@ -18,59 +18,34 @@ compared once before timing.
 
     python tools/task_bench.py [--out profiles/task/task_bench.json]
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from dynamics_bench import random_state  # noqa: E402
+import bench_common as bc  # noqa: E402
+from bench_common import ND, NG  # noqa: E402
 
 BODIES = {6: ("R_Hand",), 30: ("L_Hand", "R_Hand", "L_Ankle", "R_Ankle", "Head")}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "task", "task_bench.json"))
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
-    args = ap.parse_args()
+    args = bc.parser("profiles/task/task_bench.json").parse_args()
     import torch
-    from humanoid_amd import build
     from humanoid_amd import dynamics as D
     from humanoid_amd.body_sets import BODY_NAMES
-    from humanoid_amd.engine import Engine
-    from humanoid_amd.model import load_default_model
     from humanoid_amd.solve import Solver
     from humanoid_amd.task import TaskSpace
     n = args.envs
-    eng = Engine(load_default_model(), n, device=0)
+    eng = bc.seeded_engine(n, *bc.random_state(n, np.random.default_rng(0)))
     dev = eng.device
-    root, dof = random_state(n, np.random.default_rng(0))
-    ids = torch.arange(n, dtype=torch.int32, device=dev)
-    eng.set_root_state_indexed(torch.from_numpy(root).to(dev), ids)
-    eng.set_dof_state_indexed(torch.from_numpy(dof.reshape(n * 69, 2)).to(dev), ids)
     dyn, sol, ts = D.Dynamics(eng), Solver(eng), TaskSpace(eng)
     gen = torch.Generator(device=dev).manual_seed(1)
-    f = torch.zeros(n, 75, device=dev)
-    f[:, 6:] = (torch.rand(n, 69, device=dev, generator=gen) * 2 - 1) * 100.0
-
-    def timed(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / args.calls
+    f = torch.zeros(n, NG, device=dev)
+    f[:, 6:] = bc.uniform((n, ND), 100.0, gen)
 
     results = []
     for k, names in BODIES.items():
@@ -78,16 +53,16 @@ def main():
         rows = [(b, a) for b in bodies for a in range(6)]
         ts.set_rows(rows)
         body_idx = torch.tensor(bodies, device=dev)
-        xdd = (torch.rand(n, k, device=dev, generator=gen) * 2 - 1) * 5.0
+        xdd = bc.uniform((n, k), 5.0, gen)
         b = ts.terms(want=("bias_acc",))["bias_acc"]  # the recipe's one borrowed term
-        out_u, out_f, out_q = torch.empty(n, 75, device=dev), torch.empty(n, k, device=dev), torch.empty(n, 75, device=dev)
+        out_u, out_f, out_q = torch.empty(n, NG, device=dev), torch.empty(n, k, device=dev), torch.empty(n, NG, device=dev)
         for mode in ("force", "joint"):
             def fused():
                 return ts.control(xdd, f, mode, 0.0, out_u, out_f, out_q)
 
             def recipe():
                 dyn.refresh(jacobian=True, mass_matrix=False, bias=True)
-                J = dyn.jacobian.index_select(1, body_idx).reshape(n, k, 75)
+                J = dyn.jacobian.index_select(1, body_idx).reshape(n, k, NG)
                 Y = sol.solve(J)
                 r = xdd - ((Y @ (f - dyn.bias).unsqueeze(-1)).squeeze(-1) + b)
                 if mode == "force":
@@ -102,33 +77,18 @@ def main():
                     u = torch.cat([torch.zeros(n, 6, device=dev), (Yj.transpose(1, 2) @ F).squeeze(-1)], dim=1)
                 return u, F.squeeze(-1), sol.forward_dynamics(f + u)
 
-            for _ in range(args.warmup):
-                a, c = fused(), recipe()
-            torch.cuda.synchronize()
-            diff = {name: float((a[i] - c[i]).abs().max() / c[i].abs().max()) for i, name in ((0, "u"), (2, "qdd"))}
-            tk, tr = [], []
-            for _ in range(args.blocks):
-                tk.append(timed(fused))
-                tr.append(timed(recipe))
-            mk, mr = statistics.median(tk), statistics.median(tr)
-            results.append(dict(case=f"k{k}_{mode}", k=k, mode=mode, fused_ms=round(mk, 5),
-                                fused_blocks_ms=[round(t, 5) for t in tk], recipe_ms=round(mr, 5),
-                                recipe_blocks_ms=[round(t, 5) for t in tr], recipe_over_fused=round(mr / mk, 2),
-                                slowest_fused_over_fastest_recipe=round(max(tk) / min(tr), 4),
+            t, diff = bc.alternate(dict(fused=fused, recipe=recipe), args.warmup, args.calls, args.blocks, lambda o: {
+                name: float((o["fused"][i] - o["recipe"][i]).abs().max() / o["recipe"][i].abs().max())
+                for i, name in ((0, "u"), (2, "qdd"))})
+            tk, tr = t["fused"], t["recipe"]
+            results.append(dict(case=f"k{k}_{mode}", k=k, mode=mode, **bc.side_fields("fused", tk),
+                                **bc.side_fields("recipe", tr), recipe_over_fused=bc.over(tr, tk, 2),
+                                slowest_fused_over_fastest_recipe=bc.slowest_over_fastest(tk, tr),
                                 max_abs_difference_over_max=diff))
             print(json.dumps(results[-1]), flush=True)
-    rec = dict(tool="tools/task_bench.py", device=torch.cuda.get_device_name(0), envs=n, warmup=args.warmup,
-               calls_per_block=args.calls, blocks=args.blocks,
-               recipe="Dynamics.refresh(jacobian, bias) + row gather, Solver.solve, torch bmm / cholesky / cholesky_solve, "
-                      "Solver.forward_dynamics; b = Jdot qd borrowed from the task library, untimed",
-               task_library_device_code_id=build.device_code_id(build.LIBRARIES["task"].path),
-               solve_library_device_code_id=build.device_code_id(build.LIBRARIES["solve"].path),
-               engine_device_code_id=build.device_code_id(build.LIB), results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fo:
-        json.dump(rec, fo, indent=1)
-        fo.write("\n")
-    print("wrote", args.out)
+    bc.write_record(args.out, "tools/task_bench.py", args, ["task", "solve", "engine"], results,
+                    recipe="Dynamics.refresh(jacobian, bias) + row gather, Solver.solve, torch bmm / cholesky / cholesky_solve, "
+                           "Solver.forward_dynamics; b = Jdot qd borrowed from the task library, untimed")
 
 
 if __name__ == "__main__":
